@@ -16,6 +16,12 @@ sums.  value = chain-iterations per second over all GPUs ("MH accept-steps/sec")
 Multi-GPU: one process per GPU, chains sharded by global chain id (rank r owns ids
 [r*C, (r+1)*C)), no data-path collective; one RCCL all-gather of the per-chain ESJD /
 moment sums at the end of the timed region (weak scaling: C chains per GPU).
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  --full adds
+what else the benchmark measures: the CPU baselines, the roofline figures keyed to the
+committed counter files, and the side measurements of some workloads.  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (rank 0 of a multi-GPU run: its
+own shard), so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import ctypes as C
@@ -264,6 +270,53 @@ def counted(workload, n, K, batch=None):
         return None
 
 
+DUMP_BYTES = 64 << 20       # --dump-outputs: the size limit of one dump
+DUMP_SEED = 20261016        # --dump-outputs: the fixed sample of chains written where all of them would not fit
+
+
+def chain_sample(n, k, device):
+    """--dump-outputs: k of n chain ids (all of them when k >= n), a fixed seeded sample in increasing order"""
+    if k >= n:
+        return torch.arange(n, device=device)
+    return torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).permutation(n)[:k])).to(device)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy -- float32 stays float32, everything else (the int32 counters, the
+    float64 sums, scalars) is written as float64 -- and at most DUMP_BYTES in all; None entries are left out"""
+    host = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the limit of %d" % (total, DUMP_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def chain_outputs(chains, hist, mom, esjd, n_max=65536, hist_floats=8 << 20):
+    """--dump-outputs of a fused sampler run: the chains' state, the last launch's history rows and the streamed sums, for a
+    seeded sample of at most n_max chains (the history rows for as many of those as fit in hist_floats values)"""
+    idx = chain_sample(chains.n, n_max, chains.theta.device)
+    out = {"chain_ids": idx + chains.chain0, "theta": chains.theta[:, idx], "y": chains.y[:, idx],
+           "log_w": chains.log_w[idx], "n_moves": chains.n_moves[idx]}
+    if hist is not None:
+        k = max(1, hist_floats // (hist.shape[0] * hist.shape[1]))
+        hidx = idx[chain_sample(idx.numel(), k, idx.device)]
+        out["history_chain_ids"] = hidx + chains.chain0
+        out["history"] = hist[:, :, hidx]
+    if mom is not None:
+        out.update(sum_theta=mom.sum_theta[:, idx], sum_outer=mom.sum_outer[:, idx], sum_jump=mom.sum_jump[:, idx],
+                   moment_iters=np.float64(mom.steps))
+    if esjd is not None:
+        out["esjd"] = esjd[idx]
+    return out
+
+
 def valu_block(p, workload, kernel_ms):
     """roofline.valu: counted vector instructions x this run's kernel time, against the guide's vector issue peak"""
     d = p["derived"]
@@ -331,13 +384,17 @@ def bench_nf(args):
                         "frac": mfma_flop / (kernel_ms * 1e-3) / 1e12 / 157.3, "traffic": None,
                         "kernel": "glabc::nf_kernel<forward> + <inverse> (v_mfma_f32_32x32x2_f32)", "kernel_ms": kernel_ms,
                         "all_flop_TFLOPs": flop / (kernel_ms * 1e-3) / 1e12}}
-    pm = counted("nf", None, None)
+    pm = counted("nf", None, None) if args.full else None
     if pm is not None and "mfma" in pm:
         out["roofline"]["mfma_counters"] = {"source": "profiles/r03_pmc_nf.json (%s)" % pm["keyed_by"],
                                             "per_kernel": pm["mfma"]["per_kernel"]}
     if not args.no_cpu_baseline:
         host_blob = blob.cpu().contiguous()                   # the checker reads host memory
         out["cpu_baseline"] = cpu_baseline_nf(flow.descriptor(host_blob), rows, cur, args.couplings)
+    if args.dump_outputs:
+        si, li = chain_sample(rows, 1 << 20, z.device), chain_sample(cur, 1 << 20, z.device)     # all of them up to 209 715 chains
+        dump_outputs(args.dump_outputs, {"sample_rows": si, "sample_z": z[:, si], "sample_log_q": lq[si], "log_prob_rows": li,
+                                         "log_prob": lp[li]})
     print(json.dumps(out), flush=True)
 
 
@@ -376,23 +433,25 @@ def bench_nf_train(args):
         opt.step(x, chain_major=True)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # torch autograd + Adam, same model, a quarter of the rows
-    ref = copy.deepcopy(flow)
-    topt = torch.optim.Adam(ref.parameters(), lr=5e-4, weight_decay=1e-5)
-    xr = x[:, :rows // 4].t().contiguous()
-    def torch_step():
-        topt.zero_grad()
-        loss = ref.forward_kld(xr)
-        loss.backward()
-        topt.step()
-        return loss
-    torch_step()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(3):
+    # torch autograd + Adam, same model, a quarter of the rows (--full)
+    torch_rows_per_s = None
+    if args.full:
+        ref = copy.deepcopy(flow)
+        topt = torch.optim.Adam(ref.parameters(), lr=5e-4, weight_decay=1e-5)
+        xr = x[:, :rows // 4].t().contiguous()
+        def torch_step():
+            topt.zero_grad()
+            loss = ref.forward_kld(xr)
+            loss.backward()
+            topt.step()
+            return loss
         torch_step()
-    torch.cuda.synchronize()
-    torch_rows_per_s = 3 * (rows // 4) / (time.perf_counter() - t1)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(3):
+            torch_step()
+        torch.cuda.synchronize()
+        torch_rows_per_s = 3 * (rows // 4) / (time.perf_counter() - t1)
     mfma_flop = 4 * 2.0 * 128 * 128 * args.couplings * rows              # inverse pass + (1), (2), (3) of the backward sweep
     out = {"metric": "NF training rows/sec (forward_kld + gradient + Adam), RealNVP %d couplings" % args.couplings,
            "value": rows * args.steps / elapsed, "unit": "rows/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -400,18 +459,21 @@ def bench_nf_train(args):
            "dtype": "f32", "data": "synthetic",
            "config": {"workload": "GLMCMC_NF training step: %d couplings x MLP[1,128,128,2], %d pool rows (GLMCMC_NFs.py:112-124)"
                                   % (args.couplings, rows)},
-           "torch_autograd_rows_per_s": torch_rows_per_s, "speedup_vs_torch_autograd": rows * args.steps / elapsed / torch_rows_per_s,
+           "torch_autograd_rows_per_s": torch_rows_per_s,
+           "speedup_vs_torch_autograd": rows * args.steps / elapsed / torch_rows_per_s if torch_rows_per_s else None,
            "roofline": {"bound": "mfma", "achieved": mfma_flop / (grad_ms * 1e-3) / 1e12, "peak": 157.3, "unit": "TFLOP/s",
                         "frac": mfma_flop / (grad_ms * 1e-3) / 1e12 / 157.3, "traffic": None,
                         "kernel": "glabc::nf_kernel<inverse> + glabc::nf_backward_kernel x couplings (v_mfma_f32_32x32x2_f32)",
                         "kernel_ms": grad_ms}}
-    pm = counted("nf_train", None, None)
+    pm = counted("nf_train", None, None) if args.full else None
     if pm is not None and "mfma" in pm:
         out["roofline"]["mfma_counters"] = {"source": "profiles/r03_pmc_nf_train.json (%s)" % pm["keyed_by"],
                                             "per_kernel": pm["mfma"]["per_kernel"]}
     if not args.no_cpu_baseline:
         host_blob = flow.packed_params().cpu().contiguous()   # the checker reads host memory
         out["cpu_baseline"] = cpu_baseline_nf_train(flow.descriptor(host_blob), args.couplings)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"params": flow.packed_params(), "loss": opt.loss})
     print(json.dumps(out), flush=True)
 
 
@@ -438,6 +500,9 @@ def bench_kde(args):
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     algo_bytes = 4.0 * (3 * P + 3 * S + P)                      # points in, centres + log-weights in, densities out
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
+    if args.dump_outputs:
+        pi = chain_sample(P, 1 << 21, out.device)                  # all of them up to 262 144 chains
+        dump_outputs(args.dump_outputs, {"points": pi, "log_prob": out[pi]})
     cpu = None
     if not args.no_cpu_baseline:
         from glabcmcmc_amd import _capi
@@ -483,11 +548,11 @@ def bench_glmcmc_nf(args):
             c.l3.bias.normal_(0, 0.1)
     theta0 = torch.zeros(n, 2)
     y0 = (0.05 ** 0.5) * torch.randn(n, 2)
-    st = {}
+    st, res = {}, [None]
 
     def one_step(i):
-        g.GLMCMC_NF(m, K + 1, theta0, y0, lp, None, GF, step_size, N, None, 1 if i == 0 else 0, num_layers=args.couplings,
-                    seed=100 + i, flow=flow, return_device=True, verbose=False, state_out=st)
+        res[0] = g.GLMCMC_NF(m, K + 1, theta0, y0, lp, None, GF, step_size, N, None, 1 if i == 0 else 0, num_layers=args.couplings,
+                             seed=100 + i, flow=flow, return_device=True, verbose=False, state_out=st)
 
     for i in range(args.warmup):
         one_step(i)
@@ -515,6 +580,8 @@ def bench_glmcmc_nf(args):
                         "traffic": None, "kernel": "glabc::nf_kernel<forward, pairs> (pool draws)", "kernel_ms": None,
                         "note": "whole-loop rate: MFMA flops of the pool draws + log_prob refreshes over the wall time of the "
                                 "loop (pool weights, step kernels, host launches included); the kernel alone: --workload nf"}}
+    if args.dump_outputs:                                                # res[0]: the (num_ite, chains, d) history it returned
+        dump_outputs(args.dump_outputs, chain_outputs(st["chains"], res[0].permute(0, 2, 1), None, None))
     if not args.no_cpu_baseline:
         host_blob = flow.cpu().packed_params().cpu().contiguous()
         b = cpu_baseline_nf(flow.descriptor(host_blob), int(rows_per_iter), int(moved) + 1, args.couplings, seconds_target=10.0)
@@ -578,6 +645,8 @@ def bench_rtc(args):
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
     esjd = mom.esjd()
     ok = torch.isfinite(esjd)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, chain_outputs(chains, hist, mom, esjd))
     out = {"metric": "MH accept-steps/sec, user simulator compiled into the fused kernel at run time, 65 536 chains, dim=2",
            "value": float(n) * K * args.steps / elapsed, "unit": "chain-steps/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -613,13 +682,13 @@ def bench_aglmcmc(args):
     torch.manual_seed(0)
     theta0 = torch.zeros(n, 2)
     y0 = (0.05 ** 0.5) * torch.randn(n, 2)
-    st = {}
+    st, res = {}, [None]
 
     def one_step(i):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            g.AGLMCMC(m, K + 1, theta0, y0, lp, isir, None, 0.9, step_size, N, 0.8, 0.2, seed=50 + i, return_device=True,
-                      verbose=False, state_out=st)
+            res[0] = g.AGLMCMC(m, K + 1, theta0, y0, lp, isir, None, 0.9, step_size, N, 0.8, 0.2, seed=50 + i, return_device=True,
+                               verbose=False, state_out=st)
 
     for i in range(args.warmup):
         one_step(i)
@@ -641,6 +710,8 @@ def bench_aglmcmc(args):
            "roofline": {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
                         "kernel": "kde_log_prob_kernel<2> (dense points x centres logsumexp)", "kernel_ms": None,
                         "note": "whole-loop rate; the dominant kernel is VALU-bound O(points x centres) work, rated by --workload kde"}}
+    if args.dump_outputs:                                                # res[0]: the (num_ite, chains, d) history it returned
+        dump_outputs(args.dump_outputs, chain_outputs(st["chains"], res[0].permute(0, 2, 1), None, None))
     if not args.no_cpu_baseline:
         from glabcmcmc_amd import KernelDensity, _capi
         kde = KernelDensity(device="cuda", seed=1).fit(torch.randn(8192, 2), torch.rand(8192))
@@ -741,44 +812,49 @@ def bench_callback(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
 
-    # the two HIP kernels of an iteration, timed on their own (HIP events on the launch stream, 100 launches each)
-    lib = _capi.lib()
-    R = N * n
-    f32 = dict(dtype=torch.float32, device=dev)
-    buf = dict(theta_prop=torch.zeros(R, 2, **f32), log_q=torch.zeros(R, **f32), log_u=torch.zeros(n, **f32),
-               u_res=torch.zeros(n, dtype=torch.float64, device=dev), is_global=torch.zeros(n, dtype=torch.int32, device=dev),
-               y_prop=torch.randn(R, 2, **f32), prior_prop=-torch.rand(R, **f32), kern_prop=-torch.rand(R, **f32),
-               prior_cur=-torch.rand(n, **f32), kern_cur=-torch.rand(n, **f32))
-    io = _capi.StepIO(N, 2, 2, 0, buf["theta_prop"].data_ptr(), buf["log_q"].data_ptr(), None, buf["log_u"].data_ptr(),
-                      buf["u_res"].data_ptr(), buf["is_global"].data_ptr(), buf["y_prop"].data_ptr(), buf["prior_prop"].data_ptr(),
-                      buf["kern_prop"].data_ptr(), buf["prior_cur"].data_ptr(), buf["kern_cur"].data_ptr(), None)
-    chains = engine.ChainBatch(torch.zeros(n, 2), torch.zeros(n, 2), dev)
-    cs, ms = chains.struct(), mom.struct()
-    hist = torch.zeros(2, n, **f32)
-    run = _capi.Run()
-    run.seed, run.step0, run.n_steps, run.global_frequency, run.batch_size = 1, 1, 1, GF, N
-    run.history, run.hist_stride, run.moments = hist.data_ptr(), n, C.pointer(ms)
-    lpd, ipd = lp.descriptor(), ip.descriptor()
+    if args.dump_outputs:                 # before the per-kernel timings below, whose glabc_select launches add to the sums
+        dump_outputs(args.dump_outputs, chain_outputs(st_last["chains"], None, mom, mom.esjd()))
 
-    def timed(fn, reps=100):
-        for _ in range(5):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) / reps
+    # the two HIP kernels of an iteration, timed on their own (HIP events on the launch stream, 100 launches each; --full)
+    ms_prop = ms_sel = achieved = None
+    if args.full:
+        lib = _capi.lib()
+        R = N * n
+        f32 = dict(dtype=torch.float32, device=dev)
+        buf = dict(theta_prop=torch.zeros(R, 2, **f32), log_q=torch.zeros(R, **f32), log_u=torch.zeros(n, **f32),
+                   u_res=torch.zeros(n, dtype=torch.float64, device=dev), is_global=torch.zeros(n, dtype=torch.int32, device=dev),
+                   y_prop=torch.randn(R, 2, **f32), prior_prop=-torch.rand(R, **f32), kern_prop=-torch.rand(R, **f32),
+                   prior_cur=-torch.rand(n, **f32), kern_cur=-torch.rand(n, **f32))
+        io = _capi.StepIO(N, 2, 2, 0, buf["theta_prop"].data_ptr(), buf["log_q"].data_ptr(), None, buf["log_u"].data_ptr(),
+                          buf["u_res"].data_ptr(), buf["is_global"].data_ptr(), buf["y_prop"].data_ptr(), buf["prior_prop"].data_ptr(),
+                          buf["kern_prop"].data_ptr(), buf["prior_cur"].data_ptr(), buf["kern_cur"].data_ptr(), None)
+        chains = engine.ChainBatch(torch.zeros(n, 2), torch.zeros(n, 2), dev)
+        cs, ms = chains.struct(), mom.struct()
+        hist = torch.zeros(2, n, **f32)
+        run = _capi.Run()
+        run.seed, run.step0, run.n_steps, run.global_frequency, run.batch_size = 1, 1, 1, GF, N
+        run.history, run.hist_stride, run.moments = hist.data_ptr(), n, C.pointer(ms)
+        lpd, ipd = lp.descriptor(), ip.descriptor()
 
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    ms_prop = timed(lambda: _capi.check(lib.glabc_propose(0, C.byref(lpd), C.byref(ipd), C.byref(cs), C.byref(run), C.byref(io),
-                                                          stream), "glabc_propose"))
-    ms_sel = timed(lambda: _capi.check(lib.glabc_select(0, C.byref(ipd), C.byref(cs), C.byref(run), C.byref(io), stream),
-                                       "glabc_select"))
-    bytes_prop = 4.0 * R * (2 + 1) + n * (4 + 8 + 4) + 4.0 * n * 2
-    bytes_sel = 4.0 * R * 3 + n * (4 + 8 + 4) + n * (8 + 16) + 4.0 * n * 2 + 2 * 8.0 * 8 * n
-    achieved = (bytes_prop + bytes_sel) / ((ms_prop + ms_sel) * 1e-3) / 1e9
+        def timed(fn, reps=100):
+            for _ in range(5):
+                fn()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / reps
+
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ms_prop = timed(lambda: _capi.check(lib.glabc_propose(0, C.byref(lpd), C.byref(ipd), C.byref(cs), C.byref(run), C.byref(io),
+                                                              stream), "glabc_propose"))
+        ms_sel = timed(lambda: _capi.check(lib.glabc_select(0, C.byref(ipd), C.byref(cs), C.byref(run), C.byref(io), stream),
+                                           "glabc_select"))
+        bytes_prop = 4.0 * R * (2 + 1) + n * (4 + 8 + 4) + 4.0 * n * 2
+        bytes_sel = 4.0 * R * 3 + n * (4 + 8 + 4) + n * (8 + 16) + 4.0 * n * 2 + 2 * 8.0 * 8 * n
+        achieved = (bytes_prop + bytes_sel) / ((ms_prop + ms_sel) * 1e-3) / 1e9
     esjd = mom.esjd()
     ok = torch.isfinite(esjd)
     out = {"metric": "MH accept-steps/sec, user Model as torch callbacks (split-phase path), 65 536 chains, dim=2",
@@ -792,12 +868,14 @@ def bench_callback(args):
            "us_per_iteration": elapsed / (args.steps * K) * 1e6,
            "esjd_mean": float(esjd[ok].double().mean()),
            "mean_theta_sq": float(mom.second_moment().diagonal(dim1=1, dim2=2).mean()), "analytic_mean_theta_sq": 2.081014,
-           "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+           "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS if args.full else None,
                         "traffic": None, "kernel": "glabc::propose_kernel + glabc::select_kernel",
-                        "kernel_ms": ms_prop + ms_sel, "propose_ms": ms_prop, "select_ms": ms_sel,
-                        "algorithmic_bytes_per_launch": bytes_prop + bytes_sel,
+                        "kernel_ms": ms_prop + ms_sel if args.full else None, "propose_ms": ms_prop, "select_ms": ms_sel,
+                        "algorithmic_bytes_per_launch": bytes_prop + bytes_sel if args.full else None,
                         "note": "the two HIP kernels take %.0f us of the %.0f us of an iteration; the rest is the Model's "
-                                "~10 torch kernels and launch latency" % ((ms_prop + ms_sel) * 1e3, elapsed / (args.steps * K) * 1e6)}}
+                                "~10 torch kernels and launch latency" % ((ms_prop + ms_sel) * 1e3, elapsed / (args.steps * K) * 1e6)
+                                if args.full else "the per-kernel times: --full"}}
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_callback(n, 400)
     print(json.dumps(out), flush=True)
@@ -832,7 +910,15 @@ def main():
     ap.add_argument("--workload", default="glmcmc", choices=["glmcmc", "globalmcmc", "glmala", "nf", "gk", "kde", "callback", "glmcmc_nf", "aglmcmc", "rtc", "nf_train", "gamma"],
                     help="glmcmc = BASELINE configs[1] (the headline metric, default); globalmcmc = configs[0]'s "
                          "algorithm batched (gf 0.5); glmala = configs[2] (gf 0.8, N 5, tau 0.3, num_grad 100)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baselines, the roofline figures keyed to the committed "
+                         "counter files (profiles/), the callback workload's per-kernel timings and the nf_train workload's torch "
+                         "autograd comparison.  A plain run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; a fixed, seeded sample of the chains where the output is larger)")
     args = ap.parse_args()
+    args.no_cpu_baseline = args.no_cpu_baseline or not args.full
     if args.workload == "nf":
         return bench_nf(args)
     if args.workload == "nf_train":
@@ -961,7 +1047,8 @@ def main():
         team_geometry = args.workload in ("glmcmc", "gk", "gamma") and 2 <= args.batch <= 16 and args.lanes == 0 and \
             not (args.debug_flags & 2) and ((args.debug_flags & 4) or 16384 <= n <= 131072)
         traffic, valu = None, None
-        p = counted(args.workload + ("_fast" if args.fast_math else ""), n, K, args.batch if args.workload in ("glmcmc", "gk", "gamma") else None)
+        p = counted(args.workload + ("_fast" if args.fast_math else ""), n, K, args.batch if args.workload in ("glmcmc", "gk", "gamma") else None) \
+            if args.full else None
         if p is not None and args.lanes == 0 and args.debug_flags == 0 and not args.no_history and not args.no_moments:
             valu = valu_block(p, args.workload, kernel_ms)
             if "hbm_traffic_bytes_per_launch" in p:
@@ -1016,6 +1103,8 @@ def main():
                                   "gamma": "VALU-bound, float64: per candidate two Marsaglia-Tsang rejection loops (double log / sqrt) and four "
                                            "double-precision log(pdf) evaluations; see DESIGN.md"}[args.workload]},
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, chain_outputs(chains, hist, None if args.no_moments else mom, esjd_all))
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline() if args.workload == "glmcmc" and args.batch == NBATCH and not args.fast_math else \
                 cpu_baseline_sampler(args.workload, NBATCH if args.workload in ("globalmcmc", "glmala") else args.batch) \

@@ -7,7 +7,7 @@ tag=$1; wl=$2; shift 2
 out=$GRAFT_REPO_ROOT/gpurun_out/${tag}_${wl}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python3 bench.py --workload $wl "$@" > $out/bench.json 2> $out/bench.err
+python3 bench.py --workload $wl --full "$@" > $out/bench.json 2> $out/bench.err
 short="--workload $wl --steps 3 --warmup 1 --no-cpu-baseline $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --workload $wl --no-cpu-baseline "$@" > $out/trace.json 2> $out/trace.err
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $out/pmc_sq -- python3 bench.py $short > $out/pmc_sq.json 2> $out/pmc_sq.err
