@@ -556,6 +556,38 @@ GLABC_DEV float fast_expf(float x)
 }
 GLABC_DEV float fast_logf(float x) { return 0.6931471805599453f * __builtin_amdgcn_logf(x); }       // log(0) = -inf
 
+// ---- iSIR weights, GLMCMC.py:78-81 ------------------------------------------------------------
+// isir_weight: the specified weight, glabc_expf with NaN -> 0.  These are the bits the chain carries (w_cur) and the bits
+// the IEEE index search divides.
+// isir_weight_approx: a stand-in read ONLY by the float32 fast pass of the index search (chain_step, team_sampler_kernel),
+// whose margin absorbs it: the spec's exact reduction x = k ln2 + r, the hardware 2^(r log2e) (v_exp_f32 on |arg| <= 1/2)
+// and an exact scaling by 2^k (v_ldexp_f32, which rounds once, into the denormals too).  For EVERY float argument
+//     |approx - isir_weight| <= 1e-6 * isir_weight + 2^-149
+// (the hardware exp2's error plus the rounding of r*log2e; the 2^-149 is the rounding of both into the denormals and the
+// clamp at -104, where the exact weight is 0; tests/test_isir_weight.py sweeps all 2^32 arguments on the GPU).  NaN gives
+// the clamp's weight, at most 2^-149; above 88.7229 the exact weight is inf and this one overflows as well (>= 2^127).
+// Run-time compiled kernels (hiprtc) keep the specified weight everywhere, as before this stand-in existed: their candidate
+// loop is the code the SLP-vectorizer miscompile of DESIGN.md 4.1g and its regression test were established on.
+#if defined(__HIPCC_RTC__)
+constexpr bool kFastPassWeights = false;
+#else
+constexpr bool kFastPassWeights = true;
+#endif
+GLABC_DEV float isir_weight(float lw)
+{
+    const float v = glabc_expf(lw);
+    return (v != v) ? 0.0f : v;
+}
+GLABC_DEV float isir_weight_approx(float lw)
+{
+    const float x = __builtin_fminf(__builtin_fmaxf(lw, -104.0f), 100.0f);            // NaN -> -104
+    const float t = __builtin_fmaf(x, 0x1.715476p+0f, 12582912.0f);                   // glabc_expf_core's reduction
+    const float k = t - 12582912.0f;
+    float r = __builtin_fmaf(k, -0x1.62e4p-1f, x);
+    r = __builtin_fmaf(k, -0x1.7f7d1cp-20f, r);
+    return __builtin_ldexpf(__builtin_amdgcn_exp2f(r * 0x1.715476p+0f), (int)k);      // |k| <= 150
+}
+
 // ---- lane-group exchange -----------------------------------------------------------------
 // Groups are 1, 2 or 4 adjacent lanes, i.e. they sit inside one DPP quad: a value held by
 // group lane SRC (compile-time) reaches every lane of the group with one v_mov_b32_dpp
@@ -791,10 +823,8 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
                 log_acc = (pk - c.prior) - c.kern;                            // GLMCMC.py:96-97
             acc_mh = log_u < log_acc;                                         // GLMCMC.py:98-99
         }
-        if (ALGO == ALGO_GLMCMC) {
-            const float v = glabc_expf(lw[r]);                                // GLMCMC.py:78
-            wl[r] = (v != v) ? 0.0f : v;                                      // GLMCMC.py:80-81
-        }
+        if (ALGO == ALGO_GLMCMC)                                              // GLMCMC.py:78-81
+            wl[r] = kFastPassWeights ? isir_weight_approx(lw[r]) : isir_weight(lw[r]);
     }
 
     // ---- winner index: 0 = stay, k = candidate k-1 ----
@@ -803,13 +833,17 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
         float w[N + 1];
         w[0] = c.w_cur;                                                       // exp(log_weight_old), GLMCMC.py:75-81
         gather_weights<L, N, NL>(wl, w);
-        const float tot = aten_rowsum<N + 1>(w);                              // GLMCMC.py:82
+        float tot = aten_rowsum<N + 1>(w);                                    // GLMCMC.py:82
         const double u_res = TAPE ? a.tape_r[tape_pos] : glabc_uniform_f64(hw[2], hw[3]);
         // weight_sampling, GLMCMC.py:17-22: first k with u < sum_{j<=k} (double)(w_j / tot).  Fast pass in float32:
         // w_j * rcp(tot) is within 2.4e-7 relative of the float32 quotient (1 ulp of v_rcp_f32 + one rounding) and a
         // float32 running sum of <= 17 such terms adds <= 1e-6, so the partial sums are within 1.3e-6 of the reference's
-        // and the index can differ only if u lies that close to one of them; lanes where |u - partial sum| <= 4e-6
-        // somewhere (or anything is NaN / inf) redo it the reference's way: IEEE divisions, double sums.
+        // and the index can differ only if u lies that close to one of them.  The candidates' weights of this pass are
+        // isir_weight_approx (w_cur is exact): each within 1e-6 relative + 2^-149 of the specified one, so a partial sum
+        // S_k and the total T are within 1e-6 relative + 17 * 2^-149, and S_k / T within 2.0e-6 + 34 * 2^-149 / T of the
+        // quotient of the specified weights -- 2.0e-6 once T >= 2^-100.  1.3e-6 + 2.0e-6 < 4e-6: lanes where
+        // |u - partial sum| <= 4e-6 somewhere, or T is below 2^-100, at least 2^126 or NaN, redo it the reference's way:
+        // the specified weights, IEEE divisions, double sums.
         int ig = -1;
         bool sure = !a.exact_index;
         {
@@ -826,8 +860,18 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
             // the reciprocal is only trusted where it is accurate: a denormal / huge / zero / non-finite total shows
             // up as fast weights that do not sum to one
             sure = sure && (run > 0.999f) && (run < 1.001f);
+            if constexpr (kFastPassWeights) sure = sure && (tot >= 0x1p-100f) && (tot < 0x1p126f);
         }
         if (!sure) {
+            if constexpr (kFastPassWeights) {
+                // the specified weights of the candidates, from their log-weights on the owner lanes (the lanes of a
+                // group agree on `sure`: the whole group is here)
+                float lwg[N + 1];
+                gather_weights<L, N, NL>(lw, lwg);
+#pragma unroll
+                for (int k = 1; k <= N; ++k) w[k] = isir_weight(lwg[k]);
+                tot = aten_rowsum<N + 1>(w);
+            }
             ig = -1;
             double run = 0.0;
 #pragma unroll
@@ -850,7 +894,8 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
         const int slot = (ind - 1) / L;
         // this lane's candidate in the winning slot (conditional moves over the unrolled slots keep
         // everything in VGPRs; a run-time array index would be promoted to LDS / scratch)
-        float nt[D], ny[YD], nlw = lw[0], npr = pr[0], nkk = kk[0], nw = (ALGO == ALGO_GLMCMC) ? wl[0] : 0.0f;
+        constexpr bool CARRY_W = (ALGO == ALGO_GLMCMC) && !kFastPassWeights;  // wl holds the specified weights
+        float nt[D], ny[YD], nlw = lw[0], npr = pr[0], nkk = kk[0], nw = CARRY_W ? wl[0] : 0.0f;
 #pragma unroll
         for (int q = 0; q < D; ++q) nt[q] = th[0][q];
 #pragma unroll
@@ -865,7 +910,7 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
                 nlw = lw[r];
                 npr = pr[r];
                 nkk = kk[r];
-                if (ALGO == ALGO_GLMCMC) nw = wl[r];
+                if (CARRY_W) nw = wl[r];
             }
         }
 #pragma unroll
@@ -875,7 +920,7 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
         nlw = group_get_dyn<L>(nlw, owner);
         npr = group_get_dyn<L>(npr, owner);
         nkk = group_get_dyn<L>(nkk, owner);
-        if (ALGO == ALGO_GLMCMC) nw = group_get_dyn<L>(nw, owner);
+        if constexpr (CARRY_W) nw = group_get_dyn<L>(nw, owner);
         if (moved) {
 #pragma unroll
             for (int q = 0; q < D; ++q) c.theta[q] = nt[q];
@@ -886,7 +931,7 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
             c.q = dist_log_prob<D, GU, GM>(a.global, c.theta);
             if (ALGO == ALGO_GLMCMC) {
                 c.lw_cur = nlw;
-                c.w_cur = nw;
+                c.w_cur = CARRY_W ? nw : isir_weight(nlw);                    // the specified weight, never the fast one
                 if (is_global)
                     c.log_w = nlw;                                            // GLMCMC.py:86
                 else

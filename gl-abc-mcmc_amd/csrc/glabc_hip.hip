@@ -199,8 +199,17 @@ __global__ void __launch_bounds__(256) numerics_kernel(int op, const uint32_t* _
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (op == 6) {                                          // Philox4x32-10: (c0..c3, k0, k1) -> four words
+        const uint32_t* w = in + 6 * i;
+        const glabc_u32x4 o = glabc_philox4x32_10(w[0], w[1], w[2], w[3], w[4], w[5]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) out[4 * i + q] = o.v[q];
+        return;
+    }
     float r;
-    if (op == 0) r = glabc_expf(glabc_u2f(in[i]));
+    if (op == 7) r = isir_weight_approx(glabc_u2f(in[i]));
+    else if (op == 8) r = isir_weight(glabc_u2f(in[i]));
+    else if (op == 0) r = glabc_expf(glabc_u2f(in[i]));
     else if (op == 1) r = glabc_logf(glabc_u2f(in[i]));
     else if (op == 2 || op == 3) {
         float sn, cs;
@@ -1227,7 +1236,7 @@ __attribute__((visibility("default"))) int glabc_moments_esjd(const glabc_moment
 __attribute__((visibility("default"))) int glabc_selftest_numerics(int op, const uint32_t* in, uint32_t* out, int64_t n, void* stream)
 {
     if (!in || !out) return GLABC_ERR_NULL;
-    if (op < 0 || op > 5 || n < 0) return GLABC_ERR_ARG;
+    if (op < 0 || op > 8 || n < 0) return GLABC_ERR_ARG;
     if (n == 0) return GLABC_OK;
     hipLaunchKernelGGL(numerics_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, op, in, out, n);
     return finish_launch();

@@ -44,7 +44,7 @@ constexpr bool team_split_ok(int n, int nw) { return n >= nw && team_main_candid
 
 template <int D, int YD, int NH>
 struct TeamCand {                          // one iteration's candidates of the helper, [field][slot][lane]: conflict-free
-    float wl[NH][64];                      // exp(lw), NaN -> 0   GLMCMC.py:78-81
+    float wl[NH][64];                      // isir_weight_approx(lw) for the fast index pass (fast_expf under FAST)
     float lw[NH][64];                      // (prior' + K') - q'  GLMCMC.py:74
     float pr[NH][64];
     float kk[NH][64];
@@ -128,8 +128,12 @@ GLABC_DEV void team_candidate(const StepArgs<D, YD>& a, const Rng& rng, uint32_t
     pr = model_prior<D, YD, GU, GM>(a, th);
     kk = model_log_kernel<D, YD, GU, FAST>(a, yy);
     lw = (pr + kk) - lq;                                                      // GLMCMC.py:74
-    const float v = FAST ? fast_expf(lw) : glabc_expf(lw);                    // GLMCMC.py:78
-    wl = (v != v) ? 0.0f : v;                                                 // GLMCMC.py:80-81
+    if constexpr (FAST) {
+        const float v = fast_expf(lw);                                        // GLMCMC.py:78
+        wl = (v != v) ? 0.0f : v;                                             // GLMCMC.py:80-81
+    } else {
+        wl = kFastPassWeights ? isir_weight_approx(lw) : isir_weight(lw);     // the fast index pass only (glabc_device.h)
+    }
 }
 
 // helper wavefront: candidates LO .. HI-1 of every iteration, one iteration ahead of the main wavefront
@@ -266,7 +270,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
         for (int r = 0; r < NA; ++r) w[1 + r] = wl[r];
 #pragma unroll
         for (int r = 0; r < NH; ++r) w[1 + NA + r] = in.wl[r][lane];
-        const float tot = aten_rowsum<N + 1>(w);                                  // GLMCMC.py:82
+        float tot = aten_rowsum<N + 1>(w);                                        // GLMCMC.py:82
         const double u_res = glabc_uniform_f64(hd.v[2], hd.v[3]);
         int ig = -1;
         bool sure = !a.exact_index;
@@ -282,8 +286,16 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
                 ig = (ig < 0 && gap < 0.0f) ? k : ig;
             }
             sure = sure && (run > 0.999f) && (run < 1.001f);
+            if constexpr (!FAST && kFastPassWeights) sure = sure && (tot >= 0x1p-100f) && (tot < 0x1p126f);   // chain_step's bound
         }
         if (!sure) {
+            if constexpr (!FAST && kFastPassWeights) {                            // the specified weights (helpers' from LDS)
+#pragma unroll
+                for (int r = 0; r < NA; ++r) w[1 + r] = isir_weight(lw[r]);
+#pragma unroll
+                for (int r = 0; r < NH; ++r) w[1 + NA + r] = isir_weight(in.lw[r][lane]);
+                tot = aten_rowsum<N + 1>(w);
+            }
             ig = -1;
             double run = 0.0;
 #pragma unroll
@@ -336,7 +348,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
                 c.kern = nkk;
                 c.q = dist_log_prob<D, GU, GM>(a.global, c.theta);
                 c.lw_cur = nlw;
-                c.w_cur = nw;
+                c.w_cur = (FAST || !kFastPassWeights) ? nw : isir_weight(nlw);    // never the fast pass's weight
                 if (is_global)
                     c.log_w = nlw;                                                // GLMCMC.py:86
                 else

@@ -596,7 +596,10 @@ int glabc_kde_train_weights(const glabc_model* model, const float* theta, const 
 
 /* Test hooks (not part of the sampling API): evaluate include/glabc_numerics.h on the device.
  * op 0 expf, 1 logf, 2 sin(2 pi u), 3 cos(2 pi u) on float bit patterns in[n] -> out[n];
- * op 4 / 5: the two normals of glabc_normal_pair(in[2i], in[2i+1]).  glabc_selftest_sqrt counts the
+ * op 4 / 5: the two normals of glabc_normal_pair(in[2i], in[2i+1]);
+ * op 6: glabc_philox4x32_10(in[6i .. 6i+3], key in[6i+4], in[6i+5]) -> out[4i .. 4i+3] (n counters);
+ * op 7 / 8: the fast index pass's approximate iSIR weight / the specified one (exp, NaN -> 0) of the
+ * float bit patterns in[n].  glabc_selftest_sqrt counts the
  * floats with bit pattern in [first_bits, last_bits] whose glabc_sqrtf_normal differs from the
  * exactly rounded square root (*mismatches is a device counter the caller zeroed). */
 int glabc_selftest_numerics(int op, const uint32_t* in, uint32_t* out, int64_t n, void* stream);

@@ -62,6 +62,18 @@ typedef struct { uint32_t v[4]; } glabc_u32x4;
 #define GLABC_PHILOX_W0 0x9E3779B9u
 #define GLABC_PHILOX_W1 0xBB67AE85u
 
+/* Offline device builds for targets with a three-input bitwise op (gfx950: v_bitop3_b32) fuse each round's  hi ^ c ^ k
+ * into one instruction from round 3 on; clang emits two v_xor_b32 for it otherwise.  Rounds 1-2 keep the plain XORs: with
+ * the counter (chain_lo, chain_hi, step, slot) their operands are wave-uniform or chain-invariant, and the compiler keeps
+ * them on the scalar unit or hoists them out of the step loop, where a vector-only builtin would only add work.  Same
+ * bits.  Run-time compiled kernels (hiprtc) keep the two XORs: their candidate loop is the code the SLP-vectorizer
+ * miscompile of DESIGN.md 4.1g and its regression test were established on. */
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__HIPCC_RTC__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+#define GLABC_PHILOX_XOR3 1
+#endif
+#endif
+
 GLABC_HD glabc_u32x4 glabc_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                          uint32_t k0, uint32_t k1)
 {
@@ -69,8 +81,19 @@ GLABC_UNROLL_10
     for (int r = 0; r < 10; ++r) {
         uint64_t p0 = (uint64_t)GLABC_PHILOX_M0 * c0;
         uint64_t p1 = (uint64_t)GLABC_PHILOX_M1 * c2;
+#if defined(GLABC_PHILOX_XOR3)
+        uint32_t n0, n2;
+        if (r < 2) {
+            n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+            n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        } else {                                        /* 0x96: a ^ b ^ c */
+            n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+            n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
+        }
+#else
         uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
         uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+#endif
         c1 = (uint32_t)p1;
         c3 = (uint32_t)p0;
         c0 = n0;
