@@ -12,12 +12,24 @@
 // i.e. an explicit instantiation of sampler_kernel (glabc_sampler.h) -- the SAME template the library's built-in kernels are
 // instantiated from -- with the user's function inlined where the built-in simulators are; the host fills the same
 // StepArgs<D, YD> argument block as for the built-in kernels (glabc_pack.h).
+//
+// GLABC_RTC_WIDE (glabc_rtc_compile_wide) instantiates the lane-group GLMCMC kernel of glabc_wide.h instead, for every lanes-per-chain
+// value L = 8 / 16 / 32 / 64 the host may launch: the batch size is a launch argument there, so one program serves N = 17 .. 4096.
 #pragma once
 
 #include "glabc_sampler.h"
 
 namespace glabc {
 
+#ifdef GLABC_RTC_WIDE
+}  // namespace glabc
+#include "glabc_wide.h"
+namespace glabc {
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 8, false>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 16, false>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 32, false>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 64, false>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+#else
 template __global__ void sampler_kernel<GLABC_RTC_ALGO, GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_N, GLABC_RTC_L, VAR_GENERIC, 0>(
     const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>);
 #if GLABC_RTC_YD == GLABC_RTC_D && !defined(GLABC_USER_PRIOR) && !defined(GLABC_USER_DISCREPANCY) && !defined(GLABC_USER_KERNEL)
@@ -62,6 +74,7 @@ template __global__ void global_team_kernel<GLABC_RTC_D, GLABC_RTC_YD, VAR_GENER
 template __global__ void global_team_kernel<GLABC_RTC_D, GLABC_RTC_YD, VAR_GAUSS_UNIT, 2>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, int);
 #endif
 #endif
+#endif  // GLABC_RTC_WIDE
 
 // generate_samples(theta, 1) on rows with the noise supplied (the Model protocol's callback, for y0 and the split-phase path):
 // theta[n][D], eps[n][ND] -> y[n][YD]

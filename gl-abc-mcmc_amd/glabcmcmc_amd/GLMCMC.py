@@ -16,12 +16,20 @@ offset in a multi-GPU run), ``record_history`` (False: return None, keep only
 ``return_device`` (leave the result on the GPU), ``steps_per_launch``, ``verbose``.
 
 Dispatch (``path``): a Model and proposals that describe themselves (``descriptor()``; theta_dim 1..4 or the g-and-k
-shape; batch_size <= 4096) run in the fused kernels (above 16 proposals lane groups of a wavefront share a chain); ANY other Model object implementing the reference's callbacks
+shape; batch_size <= 4096) run in the fused kernels (above 16 proposals lane groups of a wavefront share a chain).  So does a
+``compiled.CompiledModel`` (a user's simulator compiled into those kernels at run time): up to 16 proposals in a register kernel
+compiled for the batch size, 17..4096 in the lane-group kernel compiled once per Model -- except that ``"auto"`` keeps one with a
+user prior on the split-phase path above 16 proposals (only that path redraws the 7 log(1e-10) prior sentinel), and falls back
+to it with a warning where that kernel fails to compile or fails its self-check.  ANY other Model object implementing the reference's callbacks
 (``generate_samples / prior_log_prob / calculate_log_kernel``, examples/Mixture.py:5-53), any theta_dim, any batch_size
 and any proposal object run through the split-phase path of ``generic.py`` (``glabc_propose`` -> callbacks ->
 ``glabc_select``).  ``path="generic"`` forces the latter; ``path="fused"`` raises instead of falling back.
-Generic-path extras: ``callback_device`` ('auto' | 'cuda' | 'cpu'), ``sentinel_redraw`` (GLMCMC.py:92-93, default on).
+Generic-path extras: ``callback_device`` ('auto' | 'cuda' | 'cpu'), ``sentinel_redraw`` (GLMCMC.py:92-93, default on).  A call
+that ``"auto"`` sends to a fused kernel does not take them (TypeError) -- a CompiledModel without a user prior at 17..4096
+proposals included, which ran split-phase before the lane-group kernel took such Models: pass ``path="generic"`` with them.
 """
+import warnings
+
 from . import _capi, _host, engine, generic
 
 
@@ -35,8 +43,20 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
         raise ValueError("path must be 'auto', 'fused' or 'generic'")
     if fast_math and path == "generic":
         raise ValueError("fast_math is a variant of the fused kernel (glabc_run.math_mode = GLABC_MATH_FAST)")
-    if path == "generic" or (path == "auto" and not fast_math and not generic.fused_supported(ABCset, (Local_Proposal, Importance_Proposal),
-                                                                             batch_size, _capi.MAX_BATCH_WIDE, gamma_ok=True)):
+    # fast_math names the fused kernel's variant: "auto" takes the fused path for it unconditionally
+    fused = path == "fused" or (path == "auto" and (fast_math or generic.fused_supported(ABCset, (Local_Proposal, Importance_Proposal),
+                                                                                         batch_size, _capi.MAX_BATCH_WIDE, gamma_ok=True)))
+    rtc = None
+    if fused and path == "auto" and not fast_math and int(batch_size) > _capi.MAX_BATCH and \
+            getattr(generic.try_descriptor(ABCset), "sim_kind", None) == _capi.SIM_USER:
+        from .compiled import SimulatorCompileError, SimulatorSelfCheckError
+        try:                                                       # a CompiledModel's lane-group program (compiled and checked once)
+            rtc = ABCset.program(_capi.ALGO_GLMCMC, batch_size)
+        except (SimulatorCompileError, SimulatorSelfCheckError) as exc:
+            warnings.warn("GLMCMC: the run-time compiled kernel for batch_size %d is unavailable, running the split-phase path "
+                          "instead (%s)" % (int(batch_size), str(exc).splitlines()[0]), RuntimeWarning, stacklevel=2)
+            fused = False
+    if not fused:
         return generic.run(_capi.ALGO_GLMCMC, ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Importance_Proposal,
                            filelocation, global_frequency, batch_size, "glmcmc", seed=seed, device=device, chain0=chain0,
                            record_history=record_history, stats=stats, return_device=return_device, verbose=verbose,
@@ -49,9 +69,9 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
     dev, chains, single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
     hist = _host.allocate_history(num_ite, chains, record_history)
     mirror = _host.HostMirror(hist) if _host.HostMirror.wanted(hist, single, return_device) else None   # rows leave for the host while the kernels run
-    rtc = None
     if model.sim_kind == _capi.SIM_USER:                           # compiled.CompiledModel: the simulator is run-time compiled C
-        rtc = ABCset.program(_capi.ALGO_GLMCMC, batch_size)       # (log_weight_old is computed at the first global move: `local` starts set)
+        if rtc is None:                                            # (log_weight_old is computed at the first global move: `local` starts set)
+            rtc = ABCset.program(_capi.ALGO_GLMCMC, batch_size)
     else:
         engine.init_weights(model, imp, chains)                    # GLMCMC.py:52-55
     engine.run_steps("glabc_glmcmc_steps", model, local, imp, chains, num_ite - 1, 1, engine.draw_seed(seed),

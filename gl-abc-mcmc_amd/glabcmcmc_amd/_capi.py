@@ -268,6 +268,7 @@ ENTRY_POINTS = {
     "glabc_init_weights": (C.c_int, [_P(Model), _P(Dist), _P(Chains), C.c_void_p]),
     "glabc_rtc_compile": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p,
                                     C.c_int64]),
+    "glabc_rtc_compile_wide": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),
     "glabc_rtc_steps": (C.c_int, [C.c_void_p, _P(Model), _P(Dist), _P(Dist), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_rtc_simulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_rtc_release": (None, [C.c_void_p]),

@@ -27,7 +27,14 @@ user source too: the same string may define, announced by a ``#define`` each,
     GLABC_SIMULATOR float glabc_user_log_kernel(float dis, float scale) { ... }               /* Mixture.py:38-45 */
 
 which the fused kernel then calls in place of the descriptor's forms (``prior`` stays a required argument: with a user prior it
-only says where the self-check starts its chains).  The object also
+only says where the self-check starts its chains).
+
+GLMCMC with ``batch_size`` 1..16 runs a register kernel compiled for that batch size (``glabc_rtc_compile``); with 17..4096 it runs
+the lane-group kernel of the built-in Models (8 to 64 lanes of a wavefront share a chain's proposals), compiled once per Model
+for every such batch size (``glabc_rtc_compile_wide``).  Every program is checked against the split-phase path before it is
+handed out -- the wide one once per batch size, at the lane count the library launches for it.  GLMCMC's ``path="auto"`` keeps a
+Model with a user prior on the split-phase path above 16 proposals (only that path redraws the prior's ``7 log(1e-10)``
+sentinel), and falls back to it with a warning where the wide program fails to compile or fails its check.  The object also
 implements the full duck-typed protocol (``generate_samples`` through the compiled simulator on rows, ``prior_log_prob`` /
 ``discrepancy`` / ``calculate_log_kernel`` through the row-wise kernels), so it works with every sampler, the split-phase
 path included.  Use + - * / fmaf sqrtf fabsf and the ``glabc_*`` functions of include/glabc_numerics.h (``glabc_expf``,
@@ -71,27 +78,44 @@ class CompiledModel:
         import re
         return re.search(r"define[ \t]+%s(?![A-Za-z0-9_])" % macro, self.simulator_source) is not None
 
-    # ---- run-time compiled programs, one per (algorithm, batch size) -------------------------------------------------
+    # ---- run-time compiled programs: one per (algorithm, batch size) up to 16, one wide program for GLMCMC above ---------
+    WIDE = "wide"
+
     def program(self, algo, batch_size=1):
-        key = (int(algo), 1 if algo == _capi.ALGO_GLOBALMCMC else int(batch_size))
+        algo = int(algo)
+        n = 1 if algo == _capi.ALGO_GLOBALMCMC else int(batch_size)
+        wide = algo == _capi.ALGO_GLMCMC and n > _capi.MAX_BATCH
+        if wide and n > _capi.MAX_BATCH_WIDE:
+            raise ValueError("batch_size %d: the fused kernels take 1..%d" % (n, _capi.MAX_BATCH_WIDE))
+        key = (algo, self.WIDE) if wide else (algo, n)   # the program
+        check = (algo, n)                                # its self-check: once per batch size (the wide one serves many)
         if key in self._failed:
             raise SimulatorSelfCheckError(self._failed[key])
         if key not in self._programs:
             handle = C.c_void_p()
             log = C.create_string_buffer(1 << 16)
-            rc = _capi.lib().glabc_rtc_compile(self.simulator_source.encode(), key[0], self.theta_dim, self.y_dim, self.noise_dim,
-                                               key[1], C.byref(handle), log, len(log))
+            src = self.simulator_source.encode()
+            if wide:
+                name = "glabc_rtc_compile_wide"
+                rc = _capi.lib().glabc_rtc_compile_wide(src, self.theta_dim, self.y_dim, self.noise_dim, C.byref(handle), log, len(log))
+            else:
+                name = "glabc_rtc_compile"
+                rc = _capi.lib().glabc_rtc_compile(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, C.byref(handle), log,
+                                                   len(log))
             if rc != _capi.OK:
-                raise SimulatorCompileError("glabc_rtc_compile failed (status %d):\n%s" % (rc, log.value.decode(errors="replace")))
+                raise SimulatorCompileError("%s failed (status %d):\n%s" % (name, rc, log.value.decode(errors="replace")))
             self._programs[key] = handle
-        if key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
-            self._checked.add(key)                       # before the check: self_check re-enters program() through the samplers
+        if check not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
+            self._checked.add(check)                     # before the check: self_check re-enters program() through the samplers
             try:
-                self.self_check(*key)
+                self.self_check(algo, n)
             except BaseException as exc:
                 # a program that failed (or did not finish) its check must never be handed out: release it, and keep the
-                # verdict so that every later call raises again instead of sampling with a miscompiled kernel
-                self._checked.discard(key)
+                # verdict so that every later call raises again instead of sampling with a miscompiled kernel.  The wide program
+                # is one code object for all batch sizes above 16: the checks it passed at other batch sizes go with it
+                self._checked.discard(check)
+                if wide:
+                    self._checked -= {k for k in self._checked if k[0] == algo and k[1] > _capi.MAX_BATCH}
                 handle = self._programs.pop(key, None)
                 if handle is not None:
                     _capi.lib().glabc_rtc_release(handle)
@@ -104,7 +128,8 @@ class CompiledModel:
         """The freshly compiled kernel against the split-phase path on the same Philox streams: a few iterations of
         `n_chains` synthetic chains through both (same simulator binary for the rows, library kernels for everything
         else -- the path tests/test_generic_path.py holds to the CPU checker), compared bit for bit.  Runs once per program
-        (a few ms); GLABC_RTC_SELF_CHECK=0 skips it.  It exists because the run-time compiler has miscompiled this very
+        (a few ms; the wide program once per batch size, at the lanes per chain the library launches for it);
+        GLABC_RTC_SELF_CHECK=0 skips it.  It exists because the run-time compiler has miscompiled this very
         kernel before: a mismatch raises instead of returning samples from the wrong law."""
         from .GlobalMCMC import GlobalMCMC
         from .GLMCMC import GLMCMC

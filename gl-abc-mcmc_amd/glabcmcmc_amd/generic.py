@@ -73,8 +73,16 @@ def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, ga
             gamma = True
     if gamma and not (gamma_ok and m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4):
         return False
-    if m.sim_kind == _capi.SIM_USER:                         # compiled.CompiledModel: register kernels only, compiled per batch size
-        return hasattr(ABCset, "program") and (batch_size is None or 1 <= int(batch_size) <= _capi.MAX_BATCH)
+    if m.sim_kind == _capi.SIM_USER:
+        # compiled.CompiledModel: register kernels compiled per batch size up to GLABC_MAX_BATCH; above, where the caller's entry
+        # point takes more (max_batch: GLMCMC's lane-group kernel, one program for every batch size), the wide program -- except
+        # with a user prior, which stays split-phase: a user prior may return the 7 log(1e-10) sentinel, and only the split-phase
+        # path redraws it (GLMCMC.py:92-93)
+        if not hasattr(ABCset, "program"):
+            return False
+        if batch_size is None or 1 <= int(batch_size) <= _capi.MAX_BATCH:
+            return True
+        return 1 <= int(batch_size) <= (max_batch or _capi.MAX_BATCH) and not getattr(ABCset, "user_prior", False)
     if m.sim_kind == _capi.SIM_ABS_GAUSS:                    # instantiated for theta_dim 1..8 (GLMALA and batch sizes > 16: 1..4)
         if not 1 <= m.theta_dim <= max_dim:
             return False

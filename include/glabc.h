@@ -461,6 +461,14 @@ int glabc_select(int algo, const glabc_dist* global, const glabc_chains* chains,
 typedef struct glabc_rtc_program glabc_rtc_program;
 int glabc_rtc_compile(const char* simulator_source, int32_t algo, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
                       int32_t batch_size, glabc_rtc_program** out, char* log, int64_t log_size);
+/* GLMCMC only: one program serves every batch size 17..GLABC_MAX_BATCH_WIDE (N is a launch argument of wide_kernel).  The
+ * lane-group kernel of glabc_glmcmc_steps above GLABC_MAX_BATCH (8 / 16 / 32 / 64 lanes of a wavefront share a chain's proposals)
+ * compiled around the same user source, hooks included; glabc_rtc_steps then takes run->batch_size 17..GLABC_MAX_BATCH_WIDE and
+ * run->lanes_per_chain 0 (the library's choice, as for the built-in Models), 8, 16, 32 or 64, and refuses with GLABC_ERR_ARG a
+ * batch size of 16 or less and an (N, lanes) pair whose 4 (256 / lanes) (N + 33) bytes of group rows exceed what the device
+ * gives a workgroup.  glabc_rtc_simulate / glabc_rtc_hooks / glabc_rtc_model_rows accept such a program unchanged. */
+int glabc_rtc_compile_wide(const char* simulator_source, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
+                           glabc_rtc_program** out, char* log, int64_t log_size);
 int glabc_rtc_steps(const glabc_rtc_program* program, const glabc_model* model, const glabc_dist* local, const glabc_dist* global,
                     const glabc_chains* chains, const glabc_run* run, void* stream);
 /* generate_samples(theta, 1) of the compiled simulator on n row-major points: theta[n][theta_dim], eps[n][noise_dim] -> y[n][y_dim] */
