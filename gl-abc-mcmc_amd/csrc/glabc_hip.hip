@@ -954,7 +954,7 @@ __attribute__((visibility("default"))) int glabc_dist_forward(const glabc_dist* 
         return finish_launch();                                               \
     }
     switch (dist->dim) {
-        GLABC_FWD(1) GLABC_FWD(2) GLABC_FWD(3) GLABC_FWD(4)
+        GLABC_FWD(1) GLABC_FWD(2) GLABC_FWD(3) GLABC_FWD(4) GLABC_FWD(5) GLABC_FWD(6) GLABC_FWD(7) GLABC_FWD(8)
     default: return GLABC_ERR_DIM;
     }
 #undef GLABC_FWD
@@ -1205,6 +1205,7 @@ __attribute__((visibility("default"))) int glabc_esjd(const float* history, int6
     case 6: hipLaunchKernelGGL(esjd_kernel<6>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
     case 7: hipLaunchKernelGGL(esjd_kernel<7>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
     case 8: hipLaunchKernelGGL(esjd_kernel<8>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
+    default: return GLABC_ERR_DIM;
     }
     return finish_launch();
 }
@@ -1227,6 +1228,7 @@ __attribute__((visibility("default"))) int glabc_moments_esjd(const glabc_moment
     case 6: hipLaunchKernelGGL(moments_esjd_kernel<6>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
     case 7: hipLaunchKernelGGL(moments_esjd_kernel<7>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
     case 8: hipLaunchKernelGGL(moments_esjd_kernel<8>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
+    default: return GLABC_ERR_DIM;
     }
     return finish_launch();
 }

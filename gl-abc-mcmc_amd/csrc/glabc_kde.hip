@@ -279,12 +279,12 @@ __attribute__((visibility("default"))) int glabc_kde_fit(const float* x, const f
         return GLABC_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
+#define GLABC_CASE(d) case d: hipLaunchKernelGGL((kde_fit_kernel<d>), dim3(1), dim3(256), 0, s, a); break;
     switch (dim) {
-    case 1: hipLaunchKernelGGL((kde_fit_kernel<1>), dim3(1), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((kde_fit_kernel<2>), dim3(1), dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((kde_fit_kernel<3>), dim3(1), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((kde_fit_kernel<4>), dim3(1), dim3(256), 0, s, a); break;
+        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
+    default: return GLABC_ERR_DIM;
     }
+#undef GLABC_CASE
     return launched();
 }
 
@@ -306,7 +306,10 @@ __attribute__((visibility("default"))) int glabc_kde_log_prob(const glabc_kde* k
         hipLaunchKernelGGL((kde_log_prob_kernel<d>), grid, block, 0, s, a);        \
         break;                                                                     \
     }
-    switch (kde->dim) { GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) }
+    switch (kde->dim) {
+        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
+    default: return GLABC_ERR_DIM;
+    }
 #undef GLABC_CASE
     return launched();
 }
@@ -331,7 +334,10 @@ __attribute__((visibility("default"))) int glabc_kde_log_prob_indexed(const glab
         hipLaunchKernelGGL((kde_log_prob_kernel<d>), grid, block, 0, s, a);        \
         break;                                                                     \
     }
-    switch (kde->dim) { GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) }
+    switch (kde->dim) {
+        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
+    default: return GLABC_ERR_DIM;
+    }
 #undef GLABC_CASE
     return launched();
 }
@@ -354,7 +360,10 @@ __attribute__((visibility("default"))) int glabc_kde_sample(const glabc_kde* kde
         hipLaunchKernelGGL((kde_sample_kernel<d>), grid, block, 0, s, a);          \
         break;                                                                     \
     }
-    switch (kde->dim) { GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) }
+    switch (kde->dim) {
+        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
+    default: return GLABC_ERR_DIM;
+    }
 #undef GLABC_CASE
     return launched();
 }

@@ -744,6 +744,37 @@ def kde_fixture():
     print("kde: %d arrays" % len(out))
 
 
+def kde_hidim_fixture():
+    """KernelDensity.fit / log_prob (kernel_density.py:70-128) at 5 .. 8 features, evaluated by the reference on the CPU:
+    one case per dimension, between them silverman / scott / scalar / per-dimension bandwidth, weighted and unweighted.
+    Its own generator, so that kde.npz regenerates byte for byte."""
+    import glabcmcmc.kernel_density as rkde
+    rng = np.random.default_rng(7705)
+    out = {}
+    cases = [("h5", 5, 300, True, "silverman"), ("h6", 6, 400, False, "scott"), ("h7", 7, 200, True, 0.4),
+             ("h8", 8, 350, True, torch.tensor([0.2, 0.5, 0.1, 1.5, 0.3, 0.8, 0.05, 1.0]))]
+    for tag, d, n, weighted, bw in cases:
+        X = (rng.standard_normal((n, d)) * rng.uniform(0.3, 2.0, d) + rng.uniform(-1, 1, d)).astype(np.float32)
+        w = np.exp(rng.standard_normal(n) * 1.5).astype(np.float32) if weighted else None
+        if tag == "h7":
+            w[:20] = 1e-30
+        pts = np.concatenate([X[:40] + 0.1 * rng.standard_normal((40, d)), 4 * rng.standard_normal((40, d)),
+                              60 * rng.standard_normal((16, d))]).astype(np.float32)
+        k = rkde.KernelDensity(bandwidth=bw, device="cpu")
+        k.fit(torch.from_numpy(X), None if w is None else torch.from_numpy(w))
+        lp = k.log_prob(torch.from_numpy(pts))
+        bw_out = k.bandwidth if isinstance(k.bandwidth, torch.Tensor) else torch.ones(d) * k.bandwidth
+        out.update({tag + "_X": X, tag + "_pts": pts, tag + "_bandwidth": bw_out.numpy().astype(np.float32),
+                    tag + "_weights": k.weights.numpy(), tag + "_log_prob": lp.numpy()})
+        if w is not None:
+            out[tag + "_w"] = w
+        if not isinstance(bw, str):
+            out[tag + "_bw_in"] = np.asarray(bw, np.float32).reshape(-1)
+    out["cases"] = np.array(repr([(t, d, n, wt, bw if isinstance(bw, str) else "fixed") for t, d, n, wt, bw in cases]))
+    np.savez_compressed(os.path.join(HERE, "kde_hidim.npz"), **out)
+    print("kde_hidim: %d arrays" % len(out))
+
+
 def gamma_candidates_fixture():
     """Gamma as the importance proposal INSIDE the samplers (include/glabc.h GLABC_DIST_GAMMA): the variates come from the
     chain's Gamma slots (include/glabc_numerics.h glabc_gamma_draw_candidate, through the CPU checker's test hook); the
@@ -793,6 +824,8 @@ if __name__ == "__main__":
         gamma_candidates_fixture()
     if not want or "kde" in want:
         kde_fixture()
+    if not want or "kde_hidim" in want:
+        kde_hidim_fixture()
     if not want or "aglmcmc" in want:
         aglmcmc_fixture()
     if not want or "primitives" in want:

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import torch
 
+from glabcmcmc_amd import _capi as A
 from glabcmcmc_amd import distribution
 from glabcmcmc_amd.examples.Mixture import Mixture_set
 
@@ -83,3 +84,31 @@ def mala_params(cfg):
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- KernelDensity: the checker's fit, the glabc_kde descriptor over host arrays, the rule-of-thumb factor
+def oracle_fit(oracle, X, w, h, bw_fixed):
+    n, d = X.shape
+    xs = np.ascontiguousarray(X.T)
+    weights, log_w = np.empty(n, np.float32), np.empty(n, np.float32)
+    wq, consts = np.empty(n, np.int64), np.empty(d + 2, np.float32)
+    bwp = None if bw_fixed is None else np.ascontiguousarray(bw_fixed, np.float32).ctypes.data
+    rc = oracle.oracle_kde_fit(xs.ctypes.data, None if w is None else w.ctypes.data, n, d, float(h), bwp, weights.ctypes.data,
+                               log_w.ctypes.data, wq.ctypes.data, consts.ctypes.data)
+    assert rc == 0
+    return xs, weights, log_w, wq, consts
+
+
+def kde_struct(xs, log_w, cum_q, consts, d, n):
+    k = A.Kde()
+    k.dim, k.n_samples = d, n
+    k.x, k.log_w = xs.ctypes.data, log_w.ctypes.data
+    k.cum_q = None if cum_q is None else cum_q.ctypes.data
+    for j in range(d):
+        k.bandwidth[j] = float(consts[j])
+    k.sum_log_bw, k.c_2pi = float(consts[d]), float(consts[d + 1])
+    return k
+
+
+def rule(kind, n, d):
+    return (n * (d + 2) / 4.) ** (-1. / (d + 4)) if kind == "silverman" else n ** (-1. / (d + 4))
