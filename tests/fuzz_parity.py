@@ -114,7 +114,7 @@ def one_case(rng, oracle, k):
 def one_case_mala(rng, oracle, k):
     """GLMALA: float64 state after the first accepted MALA move, wave-cooperative gradient, split fixed-point sums."""
     d = int(rng.integers(1, 5))
-    N = int(rng.integers(1, 9))
+    N = int(rng.integers(1, 17))
     eps = float(np.exp(rng.uniform(np.log(0.02), np.log(3))))
     gf = float(rng.choice([0.0, 1.0, rng.random()]))
     tau = float(np.exp(rng.uniform(np.log(0.05), np.log(0.6))))
@@ -139,12 +139,14 @@ def one_case_mala(rng, oracle, k):
     chains = engine.ChainBatch(torch.from_numpy(theta0), torch.from_numpy(y0), dev, chain0=chain0).add_mala_state()
     engine.glmala_init(model, chains)
     hist = torch.empty(T, d, n, device=dev)
-    engine.run_glmala_steps(model, glob, mala, chains, T, 1, seed, gf, N, history=hist, steps_per_launch=spl,
+    mom = engine.Moments(n, d, dev)
+    engine.run_glmala_steps(model, glob, mala, chains, T, 1, seed, gf, N, history=hist, moments=mom, steps_per_launch=spl,
                             lanes_per_chain=lanes)
     torch.cuda.synchronize()
     hc = oracle_lib.HostChains(theta0, y0, chain0=chain0).add_mala_state()
     hh = np.zeros((T, d, n), np.float32)
-    run, keep = oracle_lib.make_run(seed=seed, step0=1, n_steps=T, gf=gf, batch=N, history=hh)
+    hm = oracle_lib.HostMoments(n, d)
+    run, keep = oracle_lib.make_run(seed=seed, step0=1, n_steps=T, gf=gf, batch=N, history=hh, moments=hm)
     cs = hc.struct()
     assert oracle.oracle_glmala_init(C.byref(model), C.byref(cs)) == 0
     assert oracle.oracle_glmala_steps(C.byref(model), C.byref(glob), C.byref(mala), C.byref(cs), C.byref(run)) == 0
@@ -153,7 +155,9 @@ def one_case_mala(rng, oracle, k):
     ok = np.array_equal(bits(hist.cpu().numpy()), bits(hh)) and np.array_equal(chains.theta64.cpu().numpy(), hc.theta64) \
         and np.array_equal(chains.y64.cpu().numpy(), hc.y64) and np.array_equal(chains.log_w64.cpu().numpy(), hc.log_w64) \
         and np.array_equal(chains.grad.cpu().numpy(), hc.grad) \
-        and np.array_equal(chains.flags.cpu().numpy().astype(np.uint32), hc.flags)
+        and np.array_equal(chains.flags.cpu().numpy().astype(np.uint32), hc.flags) \
+        and np.array_equal(chains.n_moves.cpu().numpy().astype(np.uint32), hc.n_moves) \
+        and all(np.array_equal(getattr(mom, k).cpu().numpy(), getattr(hm, k)) for k in ("sum_theta", "sum_outer", "sum_jump"))
     return ok, desc, int(hc.n_moves.sum())
 
 

@@ -55,6 +55,40 @@ import oracle_lib                               # noqa: E402
 torch.set_num_threads(1)
 
 
+class AbsGauss_set(Mixture_set):
+    """The reference's Mixture example at d parameters: y = |theta| + N(0, 0.05 I), prior N(0, I), y_obs given.  Written for
+    these fixtures the way GK_set is (the reference tree has no Model of another dimension than 2 that GLMALA can run); the
+    discrepancy and the kernel are the reference's own methods, and its loops DRIVE the class."""
+
+    def __init__(self, epsilon, y_obs):
+        super().__init__(epsilon)
+        self.theta_dim = len(y_obs)
+        self.y_obs = torch.tensor([list(y_obs)], dtype=torch.float32)
+        self.y_dim = self.y_obs.shape[1]
+
+    def generate_samples(self, theta, num_samples=1):
+        d = self.theta_dim
+        likelihood = rdist.DiagGaussian(d, torch.tensor([0.0] * d), torch.log(torch.tensor([0.05] * d).sqrt()))
+        num_theta = 1 if theta.dim() == 1 else theta.shape[0]
+        if num_theta == 1:
+            return torch.abs(theta) + likelihood.sample(num_samples)
+        if num_samples == 1:
+            return torch.abs(theta) + likelihood.sample(num_theta)
+        return torch.abs(theta).unsqueeze(1).repeat(1, num_samples, 1) + \
+            likelihood.sample(num_samples * num_theta).view(num_theta, num_samples, d)
+
+    def prior_log_prob(self, samples):
+        d = self.theta_dim
+        return rdist.DiagGaussian(d, torch.tensor([0.0] * d), torch.tensor([0.0] * d)).log_prob(samples.view(-1, d))
+
+
+def model_y_obs(cfg):
+    """y_obs of a d-parameter configuration ('y_obs', or 'dim' alone: 1.5 everywhere); None = the reference's Mixture_set"""
+    if "y_obs" in cfg:
+        return list(cfg["y_obs"])
+    return [1.5] * cfg["dim"] if "dim" in cfg else None
+
+
 # --------------------------------------------------------------------------- tape
 class Tape:
     """Numbers for one chain: u[T,2] (branch, accept), r[T] f64, z[T,P,d+yd]."""
@@ -201,8 +235,9 @@ def reference_constants(cfg):
     machine's torch (log / exp differ in the last bits between CPU types): stored in the fixture so the
     tests rebuild exactly the descriptors the golden chains were produced with."""
     out = {}
-    out["c_noise_log_scale"] = torch.log(torch.tensor([0.05, 0.05]).sqrt()).numpy()                    # Mixture.py:19
-    out["c_noise_scale"] = torch.exp(torch.log(torch.tensor([0.05, 0.05]).sqrt())).numpy()
+    d = len(model_y_obs(cfg) or [0, 0])
+    out["c_noise_log_scale"] = torch.log(torch.tensor([0.05] * d).sqrt()).numpy()                      # Mixture.py:19
+    out["c_noise_scale"] = torch.exp(torch.log(torch.tensor([0.05] * d).sqrt())).numpy()
     out["c_kern_log_scale"] = torch.log(torch.tensor([cfg["epsilon"]])).numpy()                        # Mixture.py:42-43
     out["c_kern_scale"] = torch.exp(torch.log(torch.tensor([cfg["epsilon"]]))).numpy()
     for tag in ("local", "global"):
@@ -215,7 +250,10 @@ def reference_constants(cfg):
 
 
 def make_model(cfg):
-    return GK_set(cfg["epsilon"]) if cfg.get("model") == "gk" else Mixture_set(cfg["epsilon"])
+    if cfg.get("model") == "gk":
+        return GK_set(cfg["epsilon"])
+    y_obs = model_y_obs(cfg)
+    return Mixture_set(cfg["epsilon"]) if y_obs is None else AbsGauss_set(cfg["epsilon"], y_obs)
 
 
 def run_reference(algo, cfg, theta0, y0, tape):
@@ -239,7 +277,7 @@ def run_reference(algo, cfg, theta0, y0, tape):
 def sampler_fixture(name, algo, cfg, mode):
     L = oracle_lib.load()
     gk = cfg.get("model") == "gk"
-    d, yd = (4, 8) if gk else (2, 2)
+    d, yd = (4, 8) if gk else (len(model_y_obs(cfg) or [0, 0]),) * 2
     C, T, N = cfg["C"], cfg["T"], cfg["N"]
     P = N if algo in ("glmcmc", "glmala") else 1
     rng = np.random.default_rng(cfg["seed"] + 1000)
@@ -340,6 +378,24 @@ SAMPLER_FIXTURES = {
                                                   **{"global": ("uniform", [-3.0, -3.0], [3.0, 3.0])}), "philox"),
     "glmala_philox_uniform": ("glmala", dict(epsilon=0.3, gf=0.5, N=4, tau=0.3, num_grad=12, C=8, T=300, seed=35,
                                              theta0_sd=1.0, local=G2(0.35), **{"global": ("uniform", [-3.0, -3.0], [3.0, 3.0])}), "philox"),
+    # GLMALA off theta_dim 2 (AbsGauss_set above, correctly rounded sqrt: bit parity is the claim): the general branch of
+    # the wave-cooperative gradient.  A batch >= 9, a Uniform importance proposal, 0 < gf < 1, a y_obs coordinate below
+    # 2^-6 (the kernels with the general square root) and observations all away from zero (the lean ones)
+    "glmala_philox_dim1_ieee": ("glmala", dict(y_obs=[1.5], epsilon=0.3, gf=0.5, N=3, tau=0.3, num_grad=7, C=8, T=250,
+                                               seed=61, ieee_sqrt=True, theta0_sd=1.0, local=("gauss", [0.0], [0.35]),
+                                               **{"global": ("gauss", [0.0], [1.0])}), "philox"),
+    "glmala_philox_dim3_ieee": ("glmala", dict(y_obs=[1.5, 1e-3, 0.8], epsilon=0.3, gf=0.4, N=11, tau=0.25, num_grad=12,
+                                               C=8, T=250, seed=63, ieee_sqrt=True, theta0_sd=1.0,
+                                               local=("gauss", [0.0] * 3, [0.35] * 3),
+                                               **{"global": ("uniform", [-3.0] * 3, [3.0] * 3)}), "philox"),
+    "glmala_philox_dim4_ieee": ("glmala", dict(y_obs=[1.5, 0.0, 1.0, 0.5], epsilon=0.3, gf=0.6, N=9, tau=0.2, num_grad=70,
+                                               C=8, T=250, seed=64, chain0=7000000000, ieee_sqrt=True, theta0_sd=1.0,
+                                               local=("gauss", [0.0] * 4, [0.35] * 4),
+                                               **{"global": ("gauss", [0.2, -0.1, 0.0, 0.3], [1.2, 0.9, 1.0, 1.1])}), "philox"),
+    "glmala_philox_dim4_away_ieee": ("glmala", dict(dim=4, epsilon=0.4, gf=0.3, N=16, tau=0.2, num_grad=5, C=8, T=200,
+                                                    seed=65, ieee_sqrt=True, theta0_sd=1.0,
+                                                    local=("gauss", [0.0] * 4, [0.35] * 4),
+                                                    **{"global": ("gauss", [0.0] * 4, [1.0] * 4)}), "philox"),
     # BASELINE config 4's model (g-and-k, theta_dim 4, the build's own Model class) driven by the reference's loops
     "glmcmc_philox_gk": ("glmcmc", dict(model="gk", epsilon=1.0, gf=0.8, N=5, C=16, T=600, seed=51,
                                         local=("gauss", [0.0] * 4, [0.15] * 4),
@@ -571,10 +627,61 @@ def csv_fixture():
     np.savez_compressed(os.path.join(HERE, "csv.npz"), **out)
 
 
+def reference_gradient(L, model, theta, seed, chain, step, num):
+    """numberical_gradient_logABC (GLMALA.py:46-95) at one theta, noise from the Philox gradient slots (g = 1) of
+    (seed, chain, step), torch.sqrt correctly rounded (see _ieee_sqrt)"""
+    import secrets
+    d = len(theta)
+    noise = [np.zeros((num, d), np.float32) for _ in range(d)]
+    for k in range(d):
+        L.oracle_grad_noise(seed, int(chain), int(step), 1, k, num, d, noise[k].ctypes.data)
+    calls = [0]
+
+    def randn(*a, **kw):
+        k = calls[0] // 2
+        calls[0] += 1
+        return torch.from_numpy(noise[k])
+    saved = (torch.manual_seed, torch.randn, np.random.seed, secrets.randbelow, torch.sqrt)
+    torch.manual_seed, torch.randn, np.random.seed, secrets.randbelow, torch.sqrt = \
+        (lambda s: None), randn, (lambda s: None), (lambda m: 7), _ieee_sqrt
+    try:
+        out = rglmala.numberical_gradient_logABC(model, torch.from_numpy(theta), num).numpy().ravel()
+    finally:
+        torch.manual_seed, torch.randn, np.random.seed, secrets.randbelow, torch.sqrt = saved
+    assert calls[0] == 2 * d
+    return out
+
+
+GRADIENT_DIMS = {      # d -> y_obs, epsilon; num_grad walks both sides of a wavefront's 64 lanes
+    1: ([1.5], 0.05),
+    3: ([1.5, 1e-3, 0.8], 0.1),
+    4: ([1.5, 0.0, 1.0, 0.5], 0.3),
+}
+GRADIENT_DIMS_NUM = (2, 7, 63, 64, 65, 100)
+
+
+def gradient_dims_fixture():
+    """the reference's gradient at 1, 3 and 4 parameters (AbsGauss_set), 36 points each, keys 'd<d>_...'"""
+    L = oracle_lib.load()
+    out, n = {}, 36
+    for d, (y_obs, eps) in GRADIENT_DIMS.items():
+        cfg = dict(y_obs=y_obs, epsilon=eps, tau=0.3, seed=410 + d, local=("gauss", [0.0] * d, [0.35] * d),
+                   **{"global": ("gauss", [0.0] * d, [1.0] * d)})
+        rng = np.random.default_rng(410 + d)
+        theta = (rng.standard_normal((n, d)) * 1.5).astype(np.float32)
+        chain, step = rng.integers(0, 1 << 40, n), rng.integers(1, 1 << 20, n)
+        num = np.array([GRADIENT_DIMS_NUM[i % len(GRADIENT_DIMS_NUM)] for i in range(n)], np.int32)
+        model = make_model(cfg)
+        grads = np.stack([reference_gradient(L, model, theta[i], cfg["seed"], chain[i], step[i], int(num[i])) for i in range(n)])
+        grp = dict(theta=theta, chain=chain, step=step, num=num, grad=grads, cfg=np.array(repr(cfg)), **reference_constants(cfg))
+        out.update({"d%d_%s" % (d, k): v for k, v in grp.items()})
+    np.savez_compressed(os.path.join(HERE, "glmala_gradient_dims.npz"), **out)
+    print("glmala_gradient_dims: %d points at each of %s parameters" % (n, sorted(GRADIENT_DIMS)))
+
+
 def gradient_fixture():
     """numberical_gradient_logABC (GLMALA.py:46-95) on a grid of thetas, noise from the Philox gradient slots,
     torch.sqrt correctly rounded (see _ieee_sqrt)."""
-    import secrets
     L = oracle_lib.load()
     cfg = dict(epsilon=0.05, tau=0.3, num_grad=100, seed=41, local=G2(0.35), **{"global": G2(1.0)})
     rng = np.random.default_rng(41)
@@ -585,22 +692,7 @@ def gradient_fixture():
     grads = np.zeros((n, 2))
     model = Mixture_set(cfg["epsilon"])
     for i in range(n):
-        noise = [np.zeros((cfg["num_grad"], 2), np.float32) for _ in range(2)]
-        for k in range(2):
-            L.oracle_grad_noise(cfg["seed"], int(chain[i]), int(step[i]), 1, k, cfg["num_grad"], 2, noise[k].ctypes.data)
-        calls = [0]
-
-        def randn(*a, **kw):
-            k = calls[0] // 2
-            calls[0] += 1
-            return torch.from_numpy(noise[k])
-        saved = (torch.manual_seed, torch.randn, np.random.seed, secrets.randbelow, torch.sqrt)
-        torch.manual_seed, torch.randn, np.random.seed, secrets.randbelow, torch.sqrt = \
-            (lambda s: None), randn, (lambda s: None), (lambda m: 7), _ieee_sqrt
-        try:
-            grads[i] = rglmala.numberical_gradient_logABC(model, torch.from_numpy(theta[i]), cfg["num_grad"]).numpy().ravel()
-        finally:
-            torch.manual_seed, torch.randn, np.random.seed, secrets.randbelow, torch.sqrt = saved
+        grads[i] = reference_gradient(L, model, theta[i], cfg["seed"], chain[i], step[i], cfg["num_grad"])
     np.savez_compressed(os.path.join(HERE, "glmala_gradient.npz"), theta=theta, chain=chain, step=step, grad=grads,
                         cfg=np.array(repr(cfg)), **reference_constants(cfg))
     print("glmala_gradient: %d points" % n)
@@ -834,6 +926,8 @@ if __name__ == "__main__":
         csv_fixture()
     if not want or "glmala_gradient" in want:
         gradient_fixture()
+    if not want or "glmala_gradient_dims" in want:
+        gradient_dims_fixture()
     for name, (algo, cfg, mode) in SAMPLER_FIXTURES.items():
         if not want or name in want or algo in want:
             sampler_fixture(name, algo, cfg, mode)

@@ -1,4 +1,4 @@
-"""Shared helpers for the tests: golden loading and descriptor construction."""
+"""Shared helpers for the tests: golden loading, descriptor construction, output canaries."""
 import os
 
 import numpy as np
@@ -33,8 +33,36 @@ def make_dist(spec):
     raise ValueError(kind)
 
 
+class AbsGaussModel(Mixture_set):
+    """Mixture_set at d parameters: y = |theta| + N(0, 0.05 I), prior N(0, I), `y_obs` given (d = len(y_obs)) -- the Model
+    of the d-parameter GLMALA fixtures (tests/golden/make_golden.py AbsGauss_set) on the build's side, and a user's
+    descriptor Model of another dimension than 2."""
+
+    def __init__(self, epsilon, y_obs):
+        super().__init__(epsilon)
+        self.theta_dim = len(y_obs)
+        self.y_obs = torch.tensor([list(y_obs)], dtype=torch.float32)
+        self.y_dim = self.theta_dim
+
+    def _likelihood(self):
+        d = self.theta_dim
+        return distribution.DiagGaussian(d, torch.tensor([0.0] * d), torch.log(torch.tensor([0.05] * d).sqrt()))
+
+    def _prior(self):
+        d = self.theta_dim
+        return distribution.DiagGaussian(d, torch.tensor([0.0] * d), torch.tensor([0.0] * d))
+
+
+def model_y_obs(cfg):
+    """y_obs of a d-parameter configuration ('y_obs', or 'dim' alone: 1.5 everywhere); None = the 2-parameter Mixture_set"""
+    if "y_obs" in cfg:
+        return list(cfg["y_obs"])
+    return [1.5] * cfg["dim"] if "dim" in cfg else None
+
+
 def descriptors(cfg, consts=None):
-    """(model, local, global) descriptors of a test configuration.  `consts` = a golden fixture: the
+    """(model, local, global) descriptors of a test configuration; cfg['y_obs'] / cfg['dim'] select the d-parameter
+    |theta| + noise Model (AbsGaussModel), without them the reference's Mixture_set.  `consts` = a golden fixture: the
     host-computed float32 constants (exp(log_scale), log(eps) ...) are then taken from the fixture, i.e.
     the values the reference computed on the machine that generated the golden chains -- torch's CPU
     log / exp differ in the last bits between CPU types, and GLMALA's chains depend on them."""
@@ -42,11 +70,13 @@ def descriptors(cfg, consts=None):
     if gk:
         from glabcmcmc_amd.examples.GK import GK_set
         model = GK_set(cfg["epsilon"]).descriptor()
+    elif model_y_obs(cfg) is not None:
+        model = AbsGaussModel(cfg["epsilon"], model_y_obs(cfg)).descriptor()
     else:
         model = Mixture_set(cfg["epsilon"]).descriptor()
     local, glob = make_dist(cfg["local"]).descriptor(), make_dist(cfg["global"]).descriptor()
     if consts is not None:
-        for j in range(0 if gk else 2):
+        for j in range(0 if gk else model.theta_dim):
             model.noise.p1[j] = float(consts["c_noise_log_scale"][j])
             model.noise.p2[j] = float(consts["c_noise_scale"][j])
         model.kern_log_scale = float(consts["c_kern_log_scale"][0])
@@ -74,6 +104,9 @@ GLMALA_GOLDENS_EXACT = ["glmala_philox_bench_ieee", "glmala_philox_local_ieee", 
 # first sqrt-ulp event of a chain, which the float32 finite-difference prior gradient then amplifies
 GLMALA_GOLDENS_MKL = ["glmala_philox_bench", "glmala_philox_local", "glmala_philox_alllocal", "glmala_philox_uniform"]
 GLMALA_GOLDENS = GLMALA_GOLDENS_EXACT + GLMALA_GOLDENS_MKL
+# theta_dim 1, 3, 4 (make_golden.py AbsGauss_set, correctly rounded sqrt): the general branch of the cooperative gradient
+GLMALA_GOLDENS_DIMS = ["glmala_philox_dim1_ieee", "glmala_philox_dim3_ieee", "glmala_philox_dim4_ieee",
+                       "glmala_philox_dim4_away_ieee"]
 
 
 def mala_params(cfg):
@@ -84,6 +117,63 @@ def mala_params(cfg):
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def bits64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+# ---- canaries: what an output buffer holds before the call (tests/test_pool_shapes.py, tests/test_glmala_shapes.py).  After
+# GLABC_OK no element the entry point owns may still hold it, after an error every element must.
+CANARY_BITS = 0xFFC0DEAD                 # float32: a negative quiet NaN with payload 0xDEAD
+CANARY_BITS64 = 0xFFF8DEADC0DEDEAD        # float64: a negative quiet NaN with a payload no arithmetic produces
+CANARY_I64 = -0x0DEAD0C0DE0DEAD
+CANARY_I32 = -0x0DEAD0C
+
+
+def canary_f32(*shape):
+    return np.full(shape, CANARY_BITS, np.uint32).view(np.float32)
+
+
+def canary_f64(*shape):
+    return np.full(shape, CANARY_BITS64, np.uint64).view(np.float64)
+
+
+def canary_i64(*shape):
+    return np.full(shape, CANARY_I64, np.int64)
+
+
+def canary_i32(*shape):
+    return np.full(shape, CANARY_I32, np.int32)
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def host(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+def canary_left(a):
+    """number of elements that still hold the canary"""
+    a = np.asarray(a)
+    if a.dtype == np.float32:
+        return int((np.ascontiguousarray(a).view(np.uint32) == CANARY_BITS).sum())
+    if a.dtype == np.float64:
+        return int((np.ascontiguousarray(a).view(np.uint64) == CANARY_BITS64).sum())
+    return int((a == (CANARY_I64 if a.dtype == np.int64 else CANARY_I32)).sum())
+
+
+def assert_written(*arrays):
+    for a in arrays:
+        assert canary_left(a) == 0, "%d of %d elements were never written" % (canary_left(a), np.asarray(a).size)
+
+
+def assert_untouched(*arrays):
+    for a in arrays:
+        assert canary_left(a) == np.asarray(a).size, "an entry point that returned an error wrote to its output"
 
 
 # ---- KernelDensity: the checker's fit, the glabc_kde descriptor over host arrays, the rule-of-thumb factor

@@ -571,6 +571,8 @@ def test_hip_glmala_equals_oracle(hip, oracle, case, lanes):
     assert np.array_equal(chains.flags.cpu().numpy().astype(np.uint32), hc.flags)
     assert np.array_equal(chains.n_moves.cpu().numpy().astype(np.uint32), hc.n_moves)
     assert np.array_equal(mom.sum_jump.cpu().numpy(), hm.sum_jump)
+    assert np.array_equal(mom.sum_theta.cpu().numpy(), hm.sum_theta)
+    assert np.array_equal(mom.sum_outer.cpu().numpy(), hm.sum_outer)
     assert hc.n_moves.sum() > 0
 
 

@@ -7,7 +7,8 @@ import pytest
 
 import oracle_lib
 from glabcmcmc_amd import _capi as A
-from helpers import GLMALA_GOLDENS_EXACT, GLMALA_GOLDENS_MKL, SAMPLER_GOLDENS, bits, descriptors, load_golden, mala_params
+from helpers import (GLMALA_GOLDENS_DIMS, GLMALA_GOLDENS_EXACT, GLMALA_GOLDENS_MKL, SAMPLER_GOLDENS, bits, descriptors, load_golden,
+                     mala_params)
 
 # The oracle's exp/log are those of include/glabc_numerics.h, ATen's are its own vectorised
 # ones; densities agree to a few float32 ulp of the largest term, not bit for bit.
@@ -183,7 +184,7 @@ def run_oracle_glmala(oracle, g):
     cfg = g["cfg"]
     model, _, glob = descriptors(cfg, g)
     mala = mala_params(cfg)
-    C_, T, d = g["theta0"].shape[0], cfg["T"], 2
+    C_, T, d = g["theta0"].shape[0], cfg["T"], g["theta0"].shape[1]
     ch = oracle_lib.HostChains(g["theta0"], g["y0"], chain0=cfg.get("chain0", 0)).add_mala_state()
     hist = np.zeros((T, d, C_), np.float32)
     run, keep = oracle_lib.make_run(seed=cfg["seed"], step0=1, n_steps=T, gf=cfg["gf"], batch=cfg["N"], history=hist)
@@ -194,7 +195,7 @@ def run_oracle_glmala(oracle, g):
     return chains, ch
 
 
-@pytest.mark.parametrize("name", GLMALA_GOLDENS_EXACT)
+@pytest.mark.parametrize("name", GLMALA_GOLDENS_EXACT + GLMALA_GOLDENS_DIMS)
 def test_glmala_chains_bit_exact(oracle, name):
     """GLMALA.py:150-200 (iSIR + MALA with the common-random-number finite-difference gradient, the
     float32 -> float64 switch of the state, the stale iSIR weight) replayed on the same random
@@ -259,6 +260,30 @@ def test_glmala_gradient_matches_reference(oracle):
         assert oracle.oracle_numerical_gradient(C.byref(model), C.byref(mala), th.ctypes.data, cfg["seed"], int(g["chain"][i]),
                                                 int(g["step"][i]), 1, out.ctypes.data) == 0
         worst = max(worst, np.max(np.abs(out - g["grad"][i]) / np.maximum(1.0, np.abs(g["grad"][i]))))
+    assert worst < 1e-11, worst
+
+
+@pytest.mark.parametrize("d", (1, 3, 4))
+def test_glmala_gradient_matches_reference_off_two_parameters(oracle, d):
+    """The same comparison at 1, 3 and 4 parameters (tests/golden/glmala_gradient_dims.npz: the reference's
+    numberical_gradient_logABC on the d-parameter |theta| + noise Model, num_grad 2 .. 100 on both sides of 64, one y_obs
+    coordinate at 0 / 1e-3 for d = 3, 4): the bound is the 2-parameter test's."""
+    f = load_golden("glmala_gradient_dims")
+    pre = "d%d_" % d
+    g = {k[len(pre):]: v for k, v in f.items() if k.startswith(pre)}
+    cfg = eval(str(g["cfg"]), {"__builtins__": {}}, {"dict": dict})
+    assert len(cfg["y_obs"]) == d and set(g["num"]) >= {2, 7, 63, 64, 65, 100}
+    model, _, _ = descriptors(cfg, g)
+    out = np.zeros(d)
+    worst = 0.0
+    for i in range(g["theta"].shape[0]):
+        mala = mala_params(dict(cfg, num_grad=int(g["num"][i])))
+        th = np.ascontiguousarray(g["theta"][i])
+        assert oracle.oracle_numerical_gradient(C.byref(model), C.byref(mala), th.ctypes.data, cfg["seed"], int(g["chain"][i]),
+                                                int(g["step"][i]), 1, out.ctypes.data) == 0
+        assert np.isfinite(g["grad"][i]).all()
+        worst = max(worst, np.max(np.abs(out - g["grad"][i]) / np.maximum(1.0, np.abs(g["grad"][i]))))
+    print("d = %d: worst relative difference %.3g over %d points" % (d, worst, g["theta"].shape[0]))
     assert worst < 1e-11, worst
 
 

@@ -18,57 +18,16 @@ import pytest
 import torch
 
 from glabcmcmc_amd import _capi as A
-from helpers import bits, kde_struct, load_golden, make_dist, rule
+from helpers import (CANARY_I32, assert_untouched, assert_written, bits, canary_f32, canary_i32, canary_i64, canary_left,
+                     dev, host, kde_struct, load_golden, make_dist, rule)
 from test_kde import LP_ATOL, RTOL
 
-CANARY_BITS = 0xFFC0DEAD                 # float32: a negative quiet NaN with payload 0xDEAD
-CANARY_I64 = -0x0DEAD0C0DE0DEAD
-CANARY_I32 = -0x0DEAD0C
 ERR_DIM, ERR_ARG = -2, -4            # glabc_status, include/glabc.h
 
 CENTRES_CPU = (2, 63, 64, 65, 257, 3000)
 
 
-# ------------------------------------------------------------------------------------------------------- canaries
-def canary_f32(*shape):
-    return np.full(shape, CANARY_BITS, np.uint32).view(np.float32)
-
-
-def canary_i64(*shape):
-    return np.full(shape, CANARY_I64, np.int64)
-
-
-def canary_i32(*shape):
-    return np.full(shape, CANARY_I32, np.int32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def canary_left(a):
-    """number of elements that still hold the canary"""
-    a = np.asarray(a)
-    if a.dtype == np.float32:
-        return int((np.ascontiguousarray(a).view(np.uint32) == CANARY_BITS).sum())
-    return int((a == (CANARY_I64 if a.dtype == np.int64 else CANARY_I32)).sum())
-
-
-def assert_written(*arrays):
-    for a in arrays:
-        assert canary_left(a) == 0, "%d of %d elements were never written" % (canary_left(a), np.asarray(a).size)
-
-
-def assert_untouched(*arrays):
-    for a in arrays:
-        assert canary_left(a) == np.asarray(a).size, "an entry point that returned an error wrote to its output"
-
-
+# ---------------------------------------------------------------------------------- canaries (the helpers: helpers.py)
 def canary_fit(oracle, X, w, h, bw_fixed):
     """helpers.oracle_fit with canary-filled outputs (np.empty there): the checker must write all of them too"""
     n, d = X.shape
