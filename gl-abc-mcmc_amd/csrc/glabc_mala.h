@@ -661,7 +661,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) gl
                 s1[p] += (double)cur[p];
 #pragma unroll
                 for (int q = p; q < D; ++q, ++k) {
-                    s2[k] += (double)cur[p] * (double)cur[q];
+                    s2[k] = glabc_add_prod_f32(s2[k], cur[p], cur[q]);
                     double dp = (double)cur[p] - (double)prev[p];
                     double dq = (double)cur[q] - (double)prev[q];
                     sj[k] += dp * dq;
@@ -1062,7 +1062,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)
                 s1[p] += (double)cur[p];
 #pragma unroll
                 for (int q = p; q < D; ++q, ++k) {
-                    s2[k] += (double)cur[p] * (double)cur[q];
+                    s2[k] = glabc_add_prod_f32(s2[k], cur[p], cur[q]);
                     double dp = (double)cur[p] - (double)prev[p];
                     double dq = (double)cur[q] - (double)prev[q];
                     sj[k] += dp * dq;

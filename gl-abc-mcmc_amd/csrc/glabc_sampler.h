@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(BLOCK) sampler_kernel(const StepArgs<D, YD> a)
                 s1[p] += (double)c.theta[p];
 #pragma unroll
                 for (int q = p; q < D; ++q, ++k) {
-                    s2[k] += (double)c.theta[p] * (double)c.theta[q];
+                    s2[k] = glabc_add_prod_f32(s2[k], c.theta[p], c.theta[q]);
                     double dp = (double)c.theta[p] - (double)prev[p];
                     double dq = (double)c.theta[q] - (double)prev[q];
                     sj[k] += dp * dq;

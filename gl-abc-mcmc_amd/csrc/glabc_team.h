@@ -100,7 +100,9 @@ GLABC_DEV void team_candidate(const StepArgs<D, YD>& a, const Rng& rng, uint32_t
     for (int q = 0; q < D; ++q) {
         const float p0 = lc ? a.local.p0[q] : a.global.p0[q];
         const float p2 = lc ? a.local.p2[q] : a.global.p2[q];
-        const float t = p0 + p2 * e[q];                                       // distribution.py:170 / :77
+        // a candidate that cannot be the local move draws from the global proposal, whose scale the unit variant pins to
+        // exactly 1.0f (unit_scale, glabc_pack.h): x * 1.0f is x; the addition stays (it turns -0 into +0)
+        const float t = (GU && !FIRST) ? p0 + e[q] : p0 + p2 * e[q];          // distribution.py:170 / :77
         th[q] = lc ? (t + c.theta[q]) : t;                                    // GLMCMC.py:91
     }
     // a Gamma importance proposal (wave-uniform): the candidate and forward()'s log q from the chain's Gamma slots, exactly as
@@ -368,7 +370,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
                 s1[p] += (double)c.theta[p];
 #pragma unroll
                 for (int q = p; q < D; ++q, ++k) {
-                    s2[k] += (double)c.theta[p] * (double)c.theta[q];
+                    s2[k] = glabc_add_prod_f32(s2[k], c.theta[p], c.theta[q]);
                     double dp = (double)c.theta[p] - (double)prev[p];
                     double dq = (double)c.theta[q] - (double)prev[q];
                     sj[k] += dp * dq;
@@ -574,7 +576,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
                 s1[p] += (double)c.theta[p];
 #pragma unroll
                 for (int q = p; q < D; ++q, ++k) {
-                    s2[k] += (double)c.theta[p] * (double)c.theta[q];
+                    s2[k] = glabc_add_prod_f32(s2[k], c.theta[p], c.theta[q]);
                     double dp = (double)c.theta[p] - (double)prev[p];
                     double dq = (double)c.theta[q] - (double)prev[q];
                     sj[k] += dp * dq;

@@ -74,6 +74,52 @@ typedef struct { uint32_t v[4]; } glabc_u32x4;
 #endif
 #endif
 
+/* Offline device builds also evaluate the logarithm's front end and Box-Muller (below) in a form with fewer vector
+ * instructions: exact power-of-two scalings are folded into constants, signs travel as bits, and the exponent comes from
+ * v_frexp_exp_i32_f32.  Same bits as the host text, which stays the specification (tests/test_hip_boxmuller.py sweeps
+ * every radius, every angle and every positive normal argument of the logarithm).  Run-time compiled kernels keep the
+ * host text, for the reason given above, and so does an object compiled with -DGLABC_HOST_TEXT (csrc/Makefile: the two
+ * objects that measured slower with these forms). */
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__HIPCC_RTC__) && !defined(GLABC_HOST_TEXT)
+#define GLABC_DEVICE_FORMS 1
+/* a ^ (b & c) */
+GLABC_HD uint32_t glabc_xor_and(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x78);
+#else
+    return a ^ (b & c);
+#endif
+#else
+    return a ^ (b & c);
+#endif
+}
+/* Front end of glabc_logf_core for the bits ix of a positive normal float: returns the exponent e of ix re-centred on
+ * [sqrt(1/2), sqrt(2)), that is ((ix + c) >> 23) - 127 with c = 0x3f800000 - 0x3f3504f3, and in *mant the bits
+ * ((ix + c) & 0x007fffff) + 0x3f3504f3 = ix - (e << 23).  Shifted down one binade, ix + c is a finite positive float for
+ * every such ix (for the lowest ones a subnormal with bit 22 set, whose exponent v_frexp_exp_i32_f32 reports as -126,
+ * one less than the lowest normal binade's, as the formula wants).  On other bits (0, sign bit, inf, nan: callers
+ * discard the result) it is integer arithmetic on whatever exponent the instruction returns. */
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_frexp_expf) && __has_builtin(__builtin_amdgcn_mul_i24)
+#define GLABC_LOG_SPLIT_BUILTINS 1
+#endif
+#endif
+GLABC_HD int32_t glabc_log_split(uint32_t ix, uint32_t* mant)
+{
+    const uint32_t jx = ix + (0x3f800000u - 0x3f3504f3u);
+#if defined(GLABC_LOG_SPLIT_BUILTINS)
+    const int32_t e = __builtin_amdgcn_frexp_expf(glabc_u2f(jx - 0x00800000u));
+    *mant = ix + (uint32_t)__builtin_amdgcn_mul_i24(e, -8388608);        /* ix - (e << 23) in one multiply-add; |e| < 2^8 */
+#else
+    const int32_t e = (int32_t)(jx >> 23) - 127;
+    *mant = ix - ((uint32_t)e << 23);
+#endif
+    return e;
+}
+#endif
+
 GLABC_HD glabc_u32x4 glabc_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                          uint32_t k0, uint32_t k1)
 {
@@ -118,6 +164,19 @@ GLABC_HD double glabc_uniform_f64(uint32_t a, uint32_t b)
     return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * 0x1p-53;
 }
 
+/* ---- s + (double)a * (double)b for float32 a, b ---------------------------
+ * The product of two float32 values is exact in float64, so the fused form rounds once to the same double as the
+ * multiplication followed by the addition; offline device builds spend one v_fma_f64 on it instead of two instructions
+ * (-ffp-contract=off keeps the compiler from doing this by itself). */
+GLABC_HD double glabc_add_prod_f32(double s, float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__HIPCC_RTC__)
+    return __builtin_fma((double)a, (double)b, s);
+#else
+    return s + (double)a * (double)b;
+#endif
+}
+
 /* ---- f32 log ---------------------------------------------------------------
  * x = 2^e * m, m in [sqrt(1/2), sqrt(2)); log m = f - f^2/2 + f^3 P(f), f = m-1.
  * Max error < 1 ulp (measured exhaustively on (0,1] and sampled elsewhere:
@@ -126,9 +185,15 @@ GLABC_HD double glabc_uniform_f64(uint32_t a, uint32_t b)
  * and returns the same bits wherever both apply. */
 GLABC_HD float glabc_logf_core(uint32_t ix, float escale)
 {
+#if defined(GLABC_DEVICE_FORMS)
+    uint32_t im;
+    float e = (float)glabc_log_split(ix, &im) + escale;
+    float m = glabc_u2f(im);
+#else
     ix += 0x3f800000u - 0x3f3504f3u;
     float e = (float)((int32_t)(ix >> 23) - 127) + escale;
     float m = glabc_u2f((ix & 0x007fffffu) + 0x3f3504f3u);
+#endif
     float f = m - 1.0f;
     float p = -0x1.2d9544p-4f;
     p = __builtin_fmaf(p, f, 0x1.0276dcp-3f);
@@ -255,6 +320,57 @@ GLABC_HD void glabc_sincos2pi(float u, float* s_out, float* c_out)
 }
 
 /* ---- two standard normals from two u32 (Box-Muller) ------------------------- */
+#if defined(GLABC_DEVICE_FORMS)
+/* 2 * glabc_logf_normal(x), x positive normal: glabc_logf_core with every constant doubled.  Scaling by +2 commutes with
+ * every rounding (nothing under- or overflows here) and keeps every sign, zeros included; scaling by -2 would not (for
+ * x == 1 its last fma gives +0 where -2.0f * (+0) is -0), so the caller negates. */
+GLABC_HD float glabc_two_logf_normal(float x)
+{
+    uint32_t im;
+    const float e = (float)glabc_log_split(glabc_f2u(x), &im);
+    const float f = glabc_u2f(im) - 1.0f;
+    float p = 2.0f * -0x1.2d9544p-4f;
+    p = __builtin_fmaf(p, f, 2.0f * 0x1.0276dcp-3f);
+    p = __builtin_fmaf(p, f, 2.0f * -0x1.0e610cp-3f);
+    p = __builtin_fmaf(p, f, 2.0f * 0x1.235f0ep-3f);
+    p = __builtin_fmaf(p, f, 2.0f * -0x1.5467dap-3f);
+    p = __builtin_fmaf(p, f, 2.0f * 0x1.9998bp-3f);
+    p = __builtin_fmaf(p, f, 2.0f * -0x1.00023cp-2f);
+    p = __builtin_fmaf(p, f, 2.0f * 0x1.555564p-2f);
+    const float f2 = f * f;
+    float r = __builtin_fmaf(p * f, f2, e * (2.0f * 0x1.7f7d1cp-20f));
+    r = r - f2;                                                 /* 2 * fma(-0.5, f2, .) */
+    r = __builtin_fmaf(2.0f, f, r);                             /* 2 * (. + f) */
+    return __builtin_fmaf(e, 2.0f * 0x1.62e4p-1f, r);
+}
+
+/* The host text below with: u2 * 2^-24 * 4 as one multiplication; -2 log u1 as -(2 log u1), the negation a source
+ * modifier; the quadrant q read from the low mantissa bits of t + 1.5 * 2^23 (bit 0: swap; bit 1 of q and of q + 1: the
+ * signs, moved to bit 31 and XORed into the products -- a sign flip commutes with an IEEE multiplication). */
+GLABC_HD void glabc_normal_pair(uint32_t a, uint32_t b, float* z0, float* z1)
+{
+    const float u1 = glabc_uniform_pos_f32(a);
+    const float rad = glabc_sqrtf_normal(-glabc_two_logf_normal(u1));
+    const float t = (float)(b >> 8) * 0x1p-22f;
+    const float big = t + 12582912.0f;
+    const float f = t - (big - 12582912.0f);
+    const uint32_t q = glabc_f2u(big);                          /* round(t) in bits 0..2 */
+    const float x = f * 0x1.921fb6p+0f;
+    const float z = x * x;
+    float sp = -0x1.993c46p-13f;
+    sp = __builtin_fmaf(sp, z, 0x1.11072p-7f);
+    sp = __builtin_fmaf(sp, z, -0x1.555544p-3f);
+    const float s = __builtin_fmaf(sp * z, x, x);
+    float cp = 0x1.99f6ep-16f;
+    cp = __builtin_fmaf(cp, z, -0x1.6c0c5ep-10f);
+    cp = __builtin_fmaf(cp, z, 0x1.55554ap-5f);
+    const float c = __builtin_fmaf(cp * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
+    const int odd = (int32_t)(q << 31) < 0;
+    const float ss = odd ? c : s, cc = odd ? s : c;
+    *z0 = glabc_u2f(glabc_xor_and(glabc_f2u(rad * cc), (q + 1u) << 30, 0x80000000u));
+    *z1 = glabc_u2f(glabc_xor_and(glabc_f2u(rad * ss), q << 30, 0x80000000u));
+}
+#else
 GLABC_HD void glabc_normal_pair(uint32_t a, uint32_t b, float* z0, float* z1)
 {
     float u1 = glabc_uniform_pos_f32(a);
@@ -264,6 +380,7 @@ GLABC_HD void glabc_normal_pair(uint32_t a, uint32_t b, float* z0, float* z1)
     *z0 = rad * c;
     *z1 = rad * s;
 }
+#endif
 
 /* ---- f64 log / exp (GLMALA only: its gradient estimate and, once a chain has switched to
  * float64, its iSIR weights are float64 in the reference, GLMALA.py:70-95,166-169) --------------
