@@ -20,6 +20,7 @@
 
 #include "glabc_mala.h"
 #include "glabc_pack.h"
+#include "glabc_plan.h"
 #include "glabc_sampler.h"
 #include "glabc_team.h"
 
@@ -663,22 +664,47 @@ static int check_run(const glabc_model* m, const glabc_dist* local, const glabc_
     return GLABC_OK;
 }
 
-// lanes per chain: a launch-geometry choice (results do not depend on it).  Measured on MI355X
-// (profiles/): with the branch-free candidate code one wave per SIMD already interleaves its N
-// independent candidates, and one work-item per chain is fastest at 65 536 chains for N = 5
-// (6.3 ms / 2000 iterations vs 6.8 ms with 2 lanes, 9.2 ms with 4); the split only pays when a
-// launch would otherwise leave SIMDs empty (fewer chains than lanes on the chip).
-static int pick_lanes(int requested, int n_batch, int64_t n_chains)
+// The four tuning variables of the launch geometry (execution strategy only, never results), read here and nowhere else.
+// Read on EVERY call, not once per process (std::call_once): the tests flip them between launches of one process with
+// monkeypatch.setenv and must see the next launch follow.
+struct Tuning {
+    PlanKnob team_waves, team_prio;         // GLABC_TEAM_WAVES, GLABC_TEAM_PRIO: clamped by plan_launch (glabc_plan.h)
+    int mala_credit, mala_prio;             // GLABC_MALA_CREDIT, GLABC_MALA_PRIO: the GLMALA team kernel, see pack_mala
+};
+
+static Tuning read_tuning()
 {
-    int lanes = requested;
-    if (lanes <= 0) {
-        const int64_t chip_lanes = 64 * 1024;                // one wave on each of the 1024 SIMDs
-        lanes = 1;
-        while (lanes < 4 && n_chains * lanes < chip_lanes) lanes *= 2;
+    auto knob = [](const char* name) {
+        const char* e = std::getenv(name);
+        return PlanKnob{e != nullptr, e ? std::atoi(e) : 0};
+    };
+    const PlanKnob credit = knob("GLABC_MALA_CREDIT"), prio = knob("GLABC_MALA_PRIO");
+    return Tuning{knob("GLABC_TEAM_WAVES"), knob("GLABC_TEAM_PRIO"), credit.set ? std::max(-64, std::min(64, credit.value)) : 0,
+                  prio.set ? std::max(0, std::min(3, prio.value)) : 1};
+}
+
+// Launches the kernel the plan names.  Team, lane-group and max-ilp instantiations exist for theta_dim 1..4 and g-and-k (the
+// last without max-ilp objects); a plan that names one this shape does not have, or that a launcher refuses, is a defect and
+// comes back as an error -- never as a second attempt with another kernel.
+template <int D, int YD>
+static int launch_planned(const LaunchPlan& plan, int algo, const glabc_run* r, const StepArgs<D, YD>& a, hipStream_t s)
+{
+    switch (plan.kind) {
+    case PLAN_WIDE:
+        if constexpr (D <= 4) return launch_wide<D, YD>(a, r->batch_size, plan.lanes, s);
+        break;
+    case PLAN_TEAM:
+        if constexpr (D <= 4) return launch_team_dim<D, YD>(r->batch_size, plan.waves, a, plan.prio, r->math_mode == GLABC_MATH_FAST, s);
+        break;
+    case PLAN_GLOBAL_TEAM:
+        if constexpr (D <= 4) return launch_global_team_dim<D, YD>(plan.waves, a, plan.prio, s);
+        break;
+    case PLAN_LANES:
+        if (!plan.ilp) return launch_sampler_dim<D, YD, SCHED_DEFAULT>(algo, r->batch_size, plan.lanes, a, s);
+        if constexpr (D <= 4 && YD == D) return launch_sampler_dim<D, YD, SCHED_ILP>(algo, r->batch_size, plan.lanes, a, s);
+        break;
     }
-    if (lanes >= 4 && n_batch >= 3) return 4;
-    if (lanes >= 2 && n_batch >= 2) return 2;
-    return 1;
+    return GLABC_ERR_ARG;
 }
 
 static int run_sampler(int algo, const glabc_model* m, const glabc_dist* local, const glabc_dist* global,
@@ -687,96 +713,31 @@ static int run_sampler(int algo, const glabc_model* m, const glabc_dist* local, 
     int rc = check_run(m, local, global, c, r, algo == ALGO_GLMCMC);
     if (rc) return rc;
     if (c->n_chains == 0 || r->n_steps == 0) return GLABC_OK;
+    const Tuning tune = read_tuning();
+    PlanIn in = {};
+    in.algo = algo == ALGO_GLMCMC ? GLABC_ALGO_GLMCMC : GLABC_ALGO_GLOBALMCMC;
+    in.gk = m->sim_kind == GLABC_SIM_GK;
+    in.theta_dim = in.gk ? 4 : m->theta_dim;
+    in.y_dim = in.gk ? 8 : m->theta_dim;
+    in.gamma = m->prior.kind == GLABC_DIST_GAMMA || global->kind == GLABC_DIST_GAMMA;
+    in.fast = r->math_mode == GLABC_MATH_FAST;
+    in.tape = r->tape != nullptr;
+    in.debug_flags = r->debug_flags;
+    in.lanes_per_chain = r->lanes_per_chain;
+    in.batch_size = r->batch_size;
+    in.n_chains = c->n_chains;
+    in.team_waves = tune.team_waves;
+    in.team_prio = tune.team_prio;
+    const LaunchPlan plan = plan_launch(in);
+    if (plan.kind == PLAN_REFUSED) return plan.status;
     hipStream_t s = (hipStream_t)stream;
-    if (algo == ALGO_GLMCMC && r->batch_size > GLABC_MAX_BATCH) {            // glabc_wide.hip
-        if (m->sim_kind == GLABC_SIM_GK) return launch_wide<4, 8>(pack_args<4, 8>(m, local, global, c, r), r->batch_size, r->lanes_per_chain, s);
-        switch (m->theta_dim) {
-        case 1: return launch_wide<1, 1>(pack_args<1>(m, local, global, c, r), r->batch_size, r->lanes_per_chain, s);
-        case 2: return launch_wide<2, 2>(pack_args<2>(m, local, global, c, r), r->batch_size, r->lanes_per_chain, s);
-        case 3: return launch_wide<3, 3>(pack_args<3>(m, local, global, c, r), r->batch_size, r->lanes_per_chain, s);
-        case 4: return launch_wide<4, 4>(pack_args<4>(m, local, global, c, r), r->batch_size, r->lanes_per_chain, s);
-        default: return GLABC_ERR_DIM;
-        }
-    }
-    // Team geometry (glabc_team.h): two wavefronts per 64 chains, for launches that would otherwise leave the SIMDs with at most
-    // two wavefronts of sampler_kernel each.  Chosen when the caller leaves the geometry to the library.
-    const bool gamma = m->prior.kind == GLABC_DIST_GAMMA || global->kind == GLABC_DIST_GAMMA;      // VAR_GAMMA: one lane per chain, or a team of two / three wavefronts
-    const bool fast = r->math_mode == GLABC_MATH_FAST;      // runs the team kernels whatever the launch size
-    if (algo == ALGO_GLMCMC && !r->tape && !(gamma && (fast || m->sim_kind != GLABC_SIM_ABS_GAUSS)) && (fast || !(r->debug_flags & GLABC_DEBUG_NO_TEAM)) &&
-        (fast || (r->debug_flags & GLABC_DEBUG_TEAM) || (r->lanes_per_chain == 0 && c->n_chains >= 64 * 256 && c->n_chains <= 2 * 1024 * 64))) {
-        int prio = 1;                                       // the main wavefront carries the serial part of an iteration
-        if (const char* e = std::getenv("GLABC_TEAM_PRIO")) prio = std::max(0, std::min(3, std::atoi(e)));
-        // wavefronts per 64 chains: enough for about three wavefronts per SIMD (1024 SIMDs)
-        const int64_t groups = (c->n_chains + 63) / 64;
-        int nw = groups <= 1024 ? 3 : 2;
-        if (const char* e = std::getenv("GLABC_TEAM_WAVES")) nw = std::max(2, std::min(4, std::atoi(e)));
-        rc = GLABC_ERR_ARG;
-        for (; nw >= 2 && rc == GLABC_ERR_ARG; --nw) {      // fewer wavefronts when the batch is too small to split that far
-            if (m->sim_kind == GLABC_SIM_GK) {
-                rc = launch_team_dim<4, 8>(r->batch_size, nw, pack_args<4, 8>(m, local, global, c, r), prio, fast, s);
-            } else {
-                switch (m->theta_dim) {
-#define GLABC_TEAM_CASE(d) case d: rc = launch_team_dim<d, d>(r->batch_size, nw, pack_args<d>(m, local, global, c, r), prio, fast, s); break;
-                    GLABC_TEAM_CASE(1) GLABC_TEAM_CASE(2) GLABC_TEAM_CASE(3) GLABC_TEAM_CASE(4)
-#undef GLABC_TEAM_CASE
-                default: nw = 0; break;
-                }
-            }
-        }
-        if (rc != GLABC_ERR_ARG || fast) {                  // GLABC_ERR_ARG: no team kernel for this configuration (fast math: refused)
-            if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();
-            return rc;
-        }
-    }
-    // GlobalMCMC: a team of two wavefronts per 64 chains (global_team_kernel, glabc_team.h: the helper draws an iteration's random
-    // numbers one iteration ahead), for the same launch sizes and under the same debug bits
-    if (algo == ALGO_GLOBAL && !r->tape && !gamma && !(r->debug_flags & GLABC_DEBUG_NO_TEAM) &&
-        ((r->debug_flags & GLABC_DEBUG_TEAM) || (r->lanes_per_chain == 0 && c->n_chains >= 64 * 256 && c->n_chains <= 2 * 1024 * 64))) {
-        rc = GLABC_ERR_ARG;
-        int gnw = 2;                                        // (three -- the helper's work split once more -- measured slower: 1.22 against 1.17 ms)
-        if (const char* e = std::getenv("GLABC_TEAM_WAVES")) gnw = std::atoi(e) >= 3 ? 3 : 2;
-        if (m->sim_kind == GLABC_SIM_GK) {
-            rc = launch_global_team_dim<4, 8>(gnw, pack_args<4, 8>(m, local, global, c, r), 1, s);
-        } else {
-            switch (m->theta_dim) {
-#define GLABC_TEAM_CASE(d) case d: rc = launch_global_team_dim<d, d>(gnw, pack_args<d>(m, local, global, c, r), 1, s); break;
-                GLABC_TEAM_CASE(1) GLABC_TEAM_CASE(2) GLABC_TEAM_CASE(3) GLABC_TEAM_CASE(4)
-#undef GLABC_TEAM_CASE
-            default: break;
-            }
-        }
-        if (rc != GLABC_ERR_ARG) {
-            if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();
-            return rc;
-        }
-    }
-    const int lanes = (algo == ALGO_GLMCMC && !r->tape && !gamma) ? pick_lanes(r->lanes_per_chain, r->batch_size, c->n_chains) : 1;
-    // Two builds of the same kernels: up to two waves per SIMD (131 072 lanes on this part) a launch is latency-bound
-    // and runs the max-ilp schedule (217 VGPRs, 6 % faster at 65 536 chains); larger launches need the occupancy
-    // of the default schedule (126 VGPRs).  The tape variant and lane groups exist in the default objects only.
-    const bool ilp = lanes == 1 && !r->tape && !gamma && c->n_chains <= 2 * 1024 * 64 && !(r->debug_flags & GLABC_DEBUG_DEFAULT_SCHEDULE);
-    if (m->sim_kind == GLABC_SIM_GK) {
-        rc = launch_sampler_dim<4, 8, SCHED_DEFAULT>(algo, r->batch_size, lanes, pack_args<4, 8>(m, local, global, c, r), s);
-    } else {
-#define GLABC_DIM_CASE(d)                                                                                             \
-    case d:                                                                                                           \
-        rc = ilp ? launch_sampler_dim<d, d, SCHED_ILP>(algo, r->batch_size, lanes, pack_args<d>(m, local, global, c, r), s) \
-                 : launch_sampler_dim<d, d, SCHED_DEFAULT>(algo, r->batch_size, lanes, pack_args<d>(m, local, global, c, r), s); \
-        break;
-        // theta_dim 5..8: default-schedule objects only; a lane keeps (2 theta_dim + 4) registers per candidate, so the
-        // candidates are dealt to 2 / 4 lanes as soon as there are that many (the arrays would leave the registers otherwise)
-#define GLABC_HI_CASE(d)                                                                                               \
-    case d: {                                                                                                         \
-        const int hl = (algo != ALGO_GLMCMC || r->tape) ? 1 : r->lanes_per_chain ? lanes : (r->batch_size >= 3 ? 4 : r->batch_size); \
-        rc = launch_sampler_dim<d, d, SCHED_DEFAULT>(algo, r->batch_size, hl, pack_args<d>(m, local, global, c, r), s); \
-    } break;
-        switch (m->theta_dim) {
-            GLABC_DIM_CASE(1) GLABC_DIM_CASE(2) GLABC_DIM_CASE(3) GLABC_DIM_CASE(4)
-            GLABC_HI_CASE(5) GLABC_HI_CASE(6) GLABC_HI_CASE(7) GLABC_HI_CASE(8)
-        default: return GLABC_ERR_DIM;
-        }
-#undef GLABC_HI_CASE
+    switch (in.gk ? 0 : m->theta_dim) {
+#define GLABC_DIM_CASE(d) case d: rc = launch_planned<d, d>(plan, algo, r, pack_args<d>(m, local, global, c, r), s); break;
+    case 0: rc = launch_planned<4, 8>(plan, algo, r, pack_args<4, 8>(m, local, global, c, r), s); break;      // g-and-k
+        GLABC_DIM_CASE(1) GLABC_DIM_CASE(2) GLABC_DIM_CASE(3) GLABC_DIM_CASE(4)
+        GLABC_DIM_CASE(5) GLABC_DIM_CASE(6) GLABC_DIM_CASE(7) GLABC_DIM_CASE(8)
 #undef GLABC_DIM_CASE
+    default: return GLABC_ERR_DIM;
     }
     if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();
     return rc;
@@ -784,7 +745,7 @@ static int run_sampler(int algo, const glabc_model* m, const glabc_dist* local, 
 
 template <int D>
 static MalaArgs<D> pack_mala(const glabc_model* m, const glabc_dist* imp, const glabc_mala* p, const glabc_chains* c,
-                             const glabc_run* r)
+                             const glabc_run* r, int credit, int prio)
 {
     MalaArgs<D> a;
     std::memset(&a, 0, sizeof a);
@@ -803,11 +764,9 @@ static MalaArgs<D> pack_mala(const glabc_model* m, const glabc_dist* imp, const 
     // team kernel (glabc_mala.h): the main wavefront runs at s_setprio 1 -- it carries the serial part of an iteration, the helper
     // fills the issue slots it leaves (37.9 against 43.9 ms per 2000 iterations of 65 536 chains) -- and takes the same share of
     // the gradient items as a helper lane (credit 0; measured optimum, flat between -2 and +2).  GLABC_MALA_PRIO /
-    // GLABC_MALA_CREDIT override both for tuning runs -- execution strategy only, never results
-    a.credit = 0;
-    if (const char* e = std::getenv("GLABC_MALA_CREDIT")) a.credit = std::max(-64, std::min(64, std::atoi(e)));
-    a.prio = 1;
-    if (const char* e = std::getenv("GLABC_MALA_PRIO")) a.prio = std::max(0, std::min(3, std::atoi(e)));
+    // GLABC_MALA_CREDIT override both for tuning runs (read_tuning)
+    a.credit = credit;
+    a.prio = prio;
     return a;
 }
 
@@ -846,11 +805,12 @@ __attribute__((visibility("default"))) int glabc_glmala_steps(const glabc_model*
     if ((uint64_t)r->step0 + (uint64_t)r->n_steps > 0xFFFFFFFFull) return GLABC_ERR_ARG;
     if (c->n_chains == 0 || r->n_steps == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
+    const Tuning tune = read_tuning();
     switch (model->theta_dim) {
-    case 1: rc = launch_glmala_dim<1>(r->batch_size, pack_mala<1>(model, importance, mala, c, r), s); break;
-    case 2: rc = launch_glmala_dim<2>(r->batch_size, pack_mala<2>(model, importance, mala, c, r), s); break;
-    case 3: rc = launch_glmala_dim<3>(r->batch_size, pack_mala<3>(model, importance, mala, c, r), s); break;
-    case 4: rc = launch_glmala_dim<4>(r->batch_size, pack_mala<4>(model, importance, mala, c, r), s); break;
+    case 1: rc = launch_glmala_dim<1>(r->batch_size, pack_mala<1>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
+    case 2: rc = launch_glmala_dim<2>(r->batch_size, pack_mala<2>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
+    case 3: rc = launch_glmala_dim<3>(r->batch_size, pack_mala<3>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
+    case 4: rc = launch_glmala_dim<4>(r->batch_size, pack_mala<4>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
     default: return GLABC_ERR_DIM;
     }
     if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();
@@ -865,11 +825,12 @@ __attribute__((visibility("default"))) int glabc_glmala_init(const glabc_model* 
     if (rc) return rc;
     if (c->n_chains == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
+    const Tuning tune = read_tuning();
     switch (model->theta_dim) {
-    case 1: rc = launch_glmala_init_dim<1>(pack_mala<1>(model, nullptr, nullptr, c, nullptr), s); break;
-    case 2: rc = launch_glmala_init_dim<2>(pack_mala<2>(model, nullptr, nullptr, c, nullptr), s); break;
-    case 3: rc = launch_glmala_init_dim<3>(pack_mala<3>(model, nullptr, nullptr, c, nullptr), s); break;
-    case 4: rc = launch_glmala_init_dim<4>(pack_mala<4>(model, nullptr, nullptr, c, nullptr), s); break;
+    case 1: rc = launch_glmala_init_dim<1>(pack_mala<1>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
+    case 2: rc = launch_glmala_init_dim<2>(pack_mala<2>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
+    case 3: rc = launch_glmala_init_dim<3>(pack_mala<3>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
+    case 4: rc = launch_glmala_init_dim<4>(pack_mala<4>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
     default: return GLABC_ERR_DIM;
     }
     if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();

@@ -1,5 +1,6 @@
 // glabc_sampler_dim.hip -- instantiates sampler_kernel for ONE theta_dim (-DGLABC_DIM=d):
 // GLMCMC for batch sizes 1..GLABC_MAX_BATCH x lanes-per-chain {1,2,4}, GlobalMCMC (one lane).
+#include "glabc_pack.h"
 #include "glabc_sampler.h"
 
 #ifndef GLABC_DIM
@@ -13,15 +14,6 @@
 #endif
 
 namespace glabc {
-
-// the all-DiagGaussian, unit-scale prior / global configuration gets the branch-free variant
-template <int D, int YD>
-static bool gauss_unit(const StepArgs<D, YD>& a)
-{
-    const bool y_obs_away_from_zero = a.y_obs_away != 0;    // lets the variant use the lean square root (model_log_kernel)
-    return a.prior.kind == GLABC_DIST_DIAG_GAUSS && a.prior.unit_scale && a.global.kind == GLABC_DIST_DIAG_GAUSS &&
-           a.global.unit_scale && a.local.kind == GLABC_DIST_DIAG_GAUSS && y_obs_away_from_zero && a.kern_rinv != 0.0f;
-}
 
 template <int ALGO, int D, int YD, int N, int L>
 static int launch_one(const StepArgs<D, YD>& a, hipStream_t s)
@@ -42,7 +34,7 @@ static int launch_one(const StepArgs<D, YD>& a, hipStream_t s)
 #else
         return GLABC_ERR_KIND;                                      // the Gamma variant lives in the default-schedule objects
 #endif
-    } else if (YD == D && gauss_unit<D, YD>(a))
+    } else if (gauss_unit_config<D, YD>(a))
         hipLaunchKernelGGL((sampler_kernel<ALGO, D, YD, N, L, (YD == D ? VAR_GAUSS_UNIT : VAR_GENERIC), GLABC_SCHED>), dim3(grid), dim3(BLOCK), 0, s, a);
     else
         hipLaunchKernelGGL((sampler_kernel<ALGO, D, YD, N, L, VAR_GENERIC, GLABC_SCHED>), dim3(grid), dim3(BLOCK), 0, s, a);

@@ -22,25 +22,9 @@
 #pragma once
 
 #include "glabc_device.h"
+#include "glabc_geometry.h"      // the split of the candidates, the LDS budget: team_main_candidates ... team_config_ok
 
 namespace glabc {
-
-// Split of an iteration's N candidates over the NW wavefronts of a team.  The main wavefront (candidate 0 included) also draws
-// the step head and takes the decision, which cost it about 1.1 candidates (85 + 165 of 227 vector instructions); the helpers
-// share the rest evenly.  N = 5: two wavefronts 2 | 3, three wavefronts 1 | 2 2, four 1 | 2 1 1.
-constexpr int team_main_candidates(int n, int nw)
-{
-    const int t10 = (10 * n + 11) / nw - 11;               // ten times ((n + 1.1) / nw - 1.1)
-    const int na = (t10 + 5) / 10;                         // rounded
-    return na < 1 ? 1 : (na > n - (nw - 1) ? n - (nw - 1) : na);
-}
-// first candidate of helper h (h = 0 .. nw-2; h = nw-1 gives n)
-constexpr int team_helper_first(int n, int nw, int h)
-{
-    const int na = team_main_candidates(n, nw), nh = n - na, per = nh / (nw - 1), extra = nh % (nw - 1);
-    return na + h * per + (h < extra ? h : extra);
-}
-constexpr bool team_split_ok(int n, int nw) { return n >= nw && team_main_candidates(n, nw) >= 1; }
 
 template <int D, int YD, int NH>
 struct TeamCand {                          // one iteration's candidates of the helper, [field][slot][lane]: conflict-free
@@ -409,7 +393,6 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
 // simulator, prior, kernel, log q, the MH test of :44-47 / :60-61, update, Theta_Re row, sums.  65 536 chains are then two
 // wavefronts per SIMD of about half the instructions each instead of one (which issues at best every other slot).  Geometry
 // only: the draws are chain_step's words in chain_step's arithmetic, and so is everything the main wavefront computes from them.
-constexpr int GLOBAL_TEAM_CHUNK = 8;
 template <int D, int YD>
 struct GlobalDraws {                        // one iteration, [field][lane]: conflict-free
     float log_u[64];                        // log of the accept uniform (-inf for u = 0)
@@ -601,17 +584,6 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
             }
         }
     }
-}
-
-// LDS of a global_team_kernel workgroup: two chunks of GLOBAL_TEAM_CHUNK iterations' draws
-constexpr int global_team_lds_bytes(int d, int nd) { return 2 * GLOBAL_TEAM_CHUNK * (2 + d + 2 * ((nd + 1) / 2)) * 64 * 4; }
-
-// LDS of one workgroup (two iterations of the helpers' candidates); a CU hosts 1024 / 256 = 4 workgroups of a 65 536-chain launch
-constexpr int team_lds_bytes(int d, int yd, int n, int nw) { return 2 * (n - team_main_candidates(n, nw)) * (4 + d + yd) * 64 * 4; }
-constexpr int TEAM_MAX_LDS = 40 * 1024;
-constexpr bool team_config_ok(int d, int yd, int n, int nw)
-{
-    return n >= 2 && n <= GLABC_MAX_BATCH && team_split_ok(n, nw) && team_lds_bytes(d, yd, n, nw) <= TEAM_MAX_LDS;
 }
 
 #if !defined(__HIPCC_RTC__)

@@ -23,11 +23,10 @@
 // checker's bit for bit for every L, like the register kernels' (tests/test_hip_parity.py).
 #pragma once
 
+#include "glabc_geometry.h"     // WIDE_BLOCK, the group row in LDS
 #include "glabc_sampler.h"
 
 namespace glabc {
-
-constexpr int WIDE_BLOCK = 256;
 
 struct Cand {
     float lw, wl, pr, kk, log_acc;
@@ -113,7 +112,7 @@ __global__ void __launch_bounds__(WIDE_BLOCK) wide_kernel(const StepArgs<D, YD> 
     const int64_t i = valid ? chain : a.n_chains - 1;          // tail groups shadow the last chain (no stores)
     const bool writer = valid && sub == 0;
     const int n = N + 1;
-    float* w = wide_lds + (size_t)grp * (n + 32);              // this group's weights w[0..N] ...
+    float* w = wide_lds + (size_t)grp * wide_row_floats(N);     // this group's weights w[0..N] ...
     float* pbuf = w + n;                                       // ... and the 32 accumulator-lane sums of torch.sum
 
     Chain<D, YD> c;

@@ -14,7 +14,7 @@ template <int D, int YD, int L, bool GM>
 static int launch_wide_lg(const StepArgs<D, YD>& a, int N, hipStream_t s)
 {
     constexpr int GROUPS = WIDE_BLOCK / L;
-    const size_t lds = sizeof(float) * (size_t)GROUPS * (size_t)(N + 1 + 32);
+    const size_t lds = (size_t)wide_lds_bytes(L, N);
     static LdsGrant grant;                               // per instantiation, per device
     if (!grant_dynamic_lds(grant, (const void*)wide_kernel<D, YD, L, GM>, lds)) return GLABC_ERR_LAUNCH;
     const unsigned grid = (unsigned)((a.n_chains + GROUPS - 1) / GROUPS);
@@ -32,12 +32,10 @@ static int launch_wide_l(const StepArgs<D, YD>& a, int N, hipStream_t s)
     return launch_wide_lg<D, YD, L, false>(a, N, s);
 }
 
-// lanes per chain: the smallest group that keeps a lane at no more than 8 candidates (the per-step head, total and index
-// search are executed by every lane of the group, so small groups amortise them best), or the caller's choice
+// lanes: one of WIDE_LANES, from the launch plan (glabc_plan.h: the caller's choice or wide_default_lanes)
 template <int D, int YD>
 int launch_wide(const StepArgs<D, YD>& a, int N, int lanes, hipStream_t s)
 {
-    if (lanes <= 0) lanes = N <= 64 ? 8 : N <= 128 ? 16 : N <= 256 ? 32 : 64;
     switch (lanes) {
     case 8: return launch_wide_l<D, YD, 8>(a, N, s);
     case 16: return launch_wide_l<D, YD, 16>(a, N, s);

@@ -182,8 +182,11 @@ typedef struct glabc_run {
     int64_t hist_stride;           /* >= n_chains */
     const glabc_moments* moments;  /* NULL or accumulators (same stride as chains) */
     const glabc_tape* tape;        /* NULL = Philox */
-    int32_t lanes_per_chain;       /* launch geometry only, never changes results: 0 = choose, or 1 / 2 / 4 lanes cooperating on
-                                      one chain's batch_size proposals (8 / 16 / 32 / 64 when batch_size > GLABC_MAX_BATCH) */
+    int32_t lanes_per_chain;       /* launch geometry only, never changes results: 0 = the library chooses the kernel and its lanes
+                                      (DESIGN.md 4.0), or 1 / 2 / 4 lanes cooperating on one chain's batch_size proposals (8 / 16 /
+                                      32 / 64 when batch_size > GLABC_MAX_BATCH).  A non-zero value also keeps a launch off the team
+                                      kernels unless GLABC_DEBUG_TEAM asks for them; it is capped by what batch_size can feed (4
+                                      lanes need 3 proposals) and is one lane for GlobalMCMC, a tape and the Gamma variant */
     int32_t debug_flags;           /* 0, or GLABC_DEBUG_* bits: execution strategy only, never changes results */
     const uint32_t* step0_device;  /* glabc_propose / glabc_propose_redraw / glabc_select only: NULL, or a DEVICE word holding the
                                       iteration index of this call.  The kernels then read the index from it (Philox counter
@@ -223,15 +226,18 @@ typedef struct glabc_draws_out {   /* device arrays covering exactly the call's 
  * lies within 4e-6 of a partial sum (the two cannot disagree otherwise: the fast partial sums are within 1.3e-6 of
  * the reference's).  This bit takes the reference's path always -- tests use it to show both give the same chains. */
 #define GLABC_DEBUG_EXACT_INDEX 1
-/* glabc_glmcmc_steps, batch_size 2..GLABC_MAX_BATCH: launches of at most two wavefronts per SIMD run as TEAMS of two wavefronts per
- * 64 chains (csrc/glabc_team.h: one holds the chains and takes the decisions, the other evaluates half of the candidates one
- * iteration ahead).  These bits forbid / force that geometry -- tests use them to show that both give the same chains. */
+/* glabc_glmcmc_steps, batch_size 2..GLABC_MAX_BATCH: launches of 16 384 to 131 072 chains (at most two wavefronts per SIMD) with
+ * lanes_per_chain 0 run as TEAMS of three (above 65 536 chains: two) wavefronts per 64 chains (csrc/glabc_team.h: one holds the
+ * chains and takes the decisions, the others evaluate candidates one iteration ahead), or of fewer where the batch does not
+ * split that far or the candidates exceed the LDS budget.  These bits forbid / force that geometry for a launch of any size --
+ * tests use them to show that both give the same chains.  NO_TEAM wins over TEAM; GLABC_MATH_FAST ignores both; a configuration
+ * that no team fits (theta_dim 4, batch_size 12..16, say) runs one to four lanes per chain even under TEAM. */
 #define GLABC_DEBUG_NO_TEAM 2
 #define GLABC_DEBUG_TEAM 4
 /* (Round 3: teams of two / three wavefronts also run the Gamma variant, the g-and-k Model, GlobalMCMC -- glabc_globalmcmc_steps: a
  * helper wavefront draws an iteration's random numbers a chunk of iterations ahead -- and the run-time compiled kernels of
  * glabc_rtc_steps; the same two bits force / forbid the geometry there.) */
-/* One lane per chain, launches of at most two wavefronts per SIMD: the library picks the build of the kernels scheduled for
+/* One lane per chain, theta_dim 1..4 (not g-and-k), launches of at most two wavefronts per SIMD: the library picks the build of the kernels scheduled for
  * instruction-level parallelism; this bit picks the default-schedule build (the one larger launches get) -- so that a test
  * can walk EVERY instantiation with small launches (tests/test_slp_twin.py). */
 #define GLABC_DEBUG_DEFAULT_SCHEDULE 8

@@ -240,6 +240,10 @@ TEAM_CASES = [
     (3, 5, 0.7, 0.3, ("gauss", [0, 0, 0], [0.4, 0.3, 0.2]), ("gauss", [0, 0, 0], [1, 1, 1]), 300, 150),
     (3, 7, 0.7, 0.3, ("uniform", [-0.4] * 3, [0.4] * 3), ("gauss", [0.1, 0, -0.1], [1.2, 0.9, 1]), 129, 100),
     (4, 5, 0.7, 0.3, ("gauss", [0] * 4, [0.3] * 4), ("gauss", [0] * 4, [1] * 4), 300, 150),
+    # theta_dim 4 on both sides of the LDS limit (tests/test_launch_plan.py pins which kernel each row reaches): N = 8 runs teams
+    # of two and three wavefronts, N = 11 of two only, and N = 12 fits no team -- the launch falls through to sampler_kernel
+    (4, 8, 0.7, 0.3, ("gauss", [0] * 4, [0.3] * 4), ("gauss", [0] * 4, [1] * 4), 300, 150),
+    (4, 11, 0.7, 0.3, ("gauss", [0] * 4, [0.3] * 4), ("uniform", [-3] * 4, [3] * 4), 100, 80),
     (4, 12, 0.7, 0.3, ("gauss", [0] * 4, [0.3] * 4), ("uniform", [-3] * 4, [3] * 4), 100, 80),
 ]
 
