@@ -643,13 +643,16 @@ def test_model_callbacks_on_gpu(hip, oracle, prim, eps):
 
 def test_esjd_kernel(hip, oracle, prim):
     from glabcmcmc_amd import esjd
+    from test_esjd_shapes import ESJD_RTOL
     i = 0
     while "esjd_chain_%d" % i in prim:
         x = prim["esjd_chain_%d" % i]
         ref = prim["esjd_value_%d" % i]
         got = esjd(torch.from_numpy(x))
         assert got.shape == () and got.dtype == np.float32
-        assert abs(got - ref) <= (2e-5 if x.shape[1] <= 4 else 2e-4) * abs(ref), (i, got, ref)
+        # the stored values are torch's float32 results: within 1.9e-7 of the float64 value for all nine chains (condition
+        # numbers 1 .. 13), so the measured bound of tests/test_esjd_shapes.py holds here too (it was 2e-5, and 2e-4 above d = 4)
+        assert abs(got - ref) <= ESJD_RTOL * abs(ref), (i, got, ref)
         i += 1
     assert i >= 9                                          # theta_dim 5, 6 and 8 included
     assert esjd(torch.tensor([[0, 0], [1, 0], [1, 2], [1, 2], [0, 1.0]])) == np.float32(0.75)
