@@ -720,8 +720,12 @@ struct Workspace {
 
 static int64_t carve(int32_t n_couplings, int64_t n_rows, char* base, Workspace* w)
 {
-    int rows_per_wg;
-    const int wgs = wgs_for(n_rows, &rows_per_wg);
+    // one partial block per coupling and workgroup: room for the most workgroups any kernel form launches (wgs_for never returns
+    // more than min(batches, max_wgs), and the forms' batches are no smaller and their max_wgs no larger than these).  Not
+    // wgs_for's own count: that one drops when the rows per workgroup step up (512 at 65 536 rows, 257 at 65 537), and a
+    // workspace sized for a batch must hold every smaller one.
+    const int64_t batches = (n_rows + BW_ROWS - 1) / BW_ROWS;
+    const int64_t wgs = batches < 2 * BW_MAX_WGS ? batches : 2 * BW_MAX_WGS;
     int64_t at = 0;
     auto take = [&](int64_t bytes) {
         char* p = base ? base + at : nullptr;

@@ -143,9 +143,11 @@ class RealNVP(nn.Module):
         dev = self._device()
         if dev.type != "cuda":
             return self.sample_torch(num_samples, eps)
+        n = int(num_samples)
+        if n == 0:                                   # nothing to launch (an empty tensor has no address to hand over)
+            return torch.empty(0, 2, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
         blob = self.packed_params()
         f = self.descriptor(blob)
-        n = int(num_samples)
         e = None if eps is None else eps.detach().to(dev, torch.float32).t().contiguous()
         z = torch.empty(2, n, dtype=torch.float32, device=dev)
         lq = torch.empty(n, dtype=torch.float32, device=dev)
@@ -164,6 +166,8 @@ class RealNVP(nn.Module):
         f = self.descriptor(blob)
         xx = x.detach().to(dev, torch.float32).reshape(-1, 2).t().contiguous()
         lq = torch.empty(xx.shape[1], dtype=torch.float32, device=dev)
+        if xx.shape[1] == 0:
+            return lq
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             _capi.check(_capi.lib().glabc_nf_log_prob(C.byref(f), xx.data_ptr(), xx.shape[1], lq.data_ptr(),

@@ -1297,6 +1297,34 @@ ORACLE_API int oracle_nf_log_prob(const glabc_flow* f, const float* x, int64_t n
     return 0;
 }
 
+/* glabc_nf_inverse: oracle_nf_log_prob's arithmetic, and the base-space point z_out[2][n] and trace[n_couplings][n] with it
+ * (trace[c][r] = the conditioner input coupling c saw for row r); z_out and trace may be NULL */
+ORACLE_API int oracle_nf_inverse(const glabc_flow* f, const float* x, int64_t n, float* z_out, float* log_q, float* trace)
+{
+    if (!f || !f->params || !x || !log_q) return GLABC_ERR_NULL;
+    if (f->hidden != NF_H || f->n_couplings < 1) return GLABC_ERR_ARG;
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < n; ++r) {
+        float z0 = x[r], z1 = x[n + r], lq = 0.0f;
+        for (int c = f->n_couplings - 1; c >= 0; --c) {
+            float t0 = z1, t1 = z0, shift, log_s;
+            if (trace) trace[(int64_t)c * n + r] = t0;
+            nf_coupling_params(f->params + (int64_t)c * GLABC_NF_COUPLING_FLOATS, t0, &shift, &log_s);
+            z0 = t0;
+            z1 = (t1 - shift) * glabc_expf(-log_s);
+            lq = lq + (-log_s);
+        }
+        float e0 = (z0 - f->base_loc[0]) / f->base_scale[0], e1 = (z1 - f->base_loc[1]) / f->base_scale[1];
+        float lp = f->base_c0 - ((f->base_log_scale[0] + 0.5f * (e0 * e0)) + (f->base_log_scale[1] + 0.5f * (e1 * e1)));
+        log_q[r] = lq + lp;
+        if (z_out) {
+            z_out[r] = z0;
+            z_out[n + r] = z1;
+        }
+    }
+    return 0;
+}
+
 
 /* ---- the training step of GLMCMC_NFs.py:63,112-124: loss = forward_kld(x) = -mean(log_prob(x)), its gradient, Adam --------
  * The reference differentiates with autograd; this is the same derivative written out (chain rule through

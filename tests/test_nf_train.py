@@ -130,7 +130,8 @@ def hip_gradient(flow_dev, x_rows):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_couplings,n", [(1, 100), (3, 4096 + 37), (8, 1000), (2, 70001), (32, 300)])
+@pytest.mark.parametrize("n_couplings,n", [(1, 100), (3, 4096 + 37), (8, 1000), (2, 70001), (32, 300),
+                                           (2, 127), (2, 128), (2, 129), (2, 257)])   # a 128-row batch of GLABC_NF_BW=1|4, +-1; two
 def test_hip_gradient_matches_the_checker(hip, oracle, n_couplings, n):
     flow = trained_looking_flow(n_couplings, 11 + n_couplings)
     x = torch.randn(n, 2, generator=torch.Generator().manual_seed(n)) * 1.3
@@ -233,13 +234,15 @@ def test_hip_training_lowers_the_forward_kl(hip):
 def test_hip_gradient_other_kernel_forms(hip, variant):
     """GLABC_NF_BW selects the form of the backward kernel once per process (8 = default; 4 = the sign-bit kernel as two 4-wave
     workgroups per CU; 1 = the form that stages a2 itself): the measuring knobs pass the same gradient check, in a child
-    process of their own"""
+    process of their own -- at their own batch boundaries (128 rows: n = 127, 128, 129, 257) as well, and with a workspace of
+    exactly the advertised size and a canary behind it (tests/test_nf_shapes.py::test_grad_workspace_is_exactly_enough)"""
     import os
     import subprocess
     import sys
     env = dict(os.environ, GLABC_NF_BW=variant)
     here = os.path.abspath(__file__)
-    run = subprocess.run([sys.executable, "-m", "pytest", here, "-q", "-x", "-m", "gpu", "-k",
-                          "test_hip_gradient_matches_the_checker and (3-4133 or 2-70001)"], env=env, capture_output=True, text=True,
-                         timeout=600)
-    assert run.returncode == 0 and "2 passed" in run.stdout, run.stdout[-2000:] + run.stderr[-2000:]
+    shapes = os.path.join(os.path.dirname(here), "test_nf_shapes.py")
+    run = subprocess.run([sys.executable, "-m", "pytest", here, shapes, "-q", "-x", "-m", "gpu", "-k",
+                          "(test_hip_gradient_matches_the_checker and (3-4133 or 2-70001 or 2-127 or 2-128 or 2-129 or 2-257))"
+                          " or test_grad_workspace_is_exactly_enough"], env=env, capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and "9 passed" in run.stdout, run.stdout[-2000:] + run.stderr[-2000:]
