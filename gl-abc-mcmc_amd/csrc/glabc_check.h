@@ -1,0 +1,116 @@
+// glabc_check.h -- the argument checks the entry points of include/glabc.h share, as pure functions of the descriptors
+// (no HIP: tests/test_arg_checks.py compiles this header with g++).  Each returns GLABC_OK or the status the entry point
+// returns; an entry point calls them in the order its own contract lists the checks and keeps inline what only it asks.
+#pragma once
+
+#include <cmath>
+
+#include "../../include/glabc.h"
+
+namespace glabc {
+
+// allow_gamma: GLABC_DIST_GAMMA is known where include/glabc.h says so (importance / global proposal and prior of
+// glabc_glmcmc_steps / glabc_globalmcmc_steps / glabc_init_weights, glabc_dist_log_prob, the row-wise Model callbacks, the
+// global proposal of the split-phase entry points).  dim: the dimension the caller expects, or 0 for any of 1..GLABC_MAX_DIM
+inline int check_dist(const glabc_dist* g, int dim, bool allow_gamma = false)
+{
+    if (!g) return GLABC_ERR_NULL;
+    if (g->dim < 1 || g->dim > GLABC_MAX_DIM || (dim > 0 && g->dim != dim)) return GLABC_ERR_DIM;
+    if (g->kind == GLABC_DIST_GAMMA) {
+        if (!allow_gamma) return GLABC_ERR_KIND;
+        for (int j = 0; j < g->dim; ++j)            // shape, rate, scale = 1/rate > 0 and finite; gammaln(shape) finite
+            if (!(g->p0[j] > 0.0f) || !std::isfinite(g->p0[j]) || !(g->p1[j] > 0.0f) || !std::isfinite(g->p1[j]) ||
+                !(g->p2[j] > 0.0f) || !std::isfinite(g->p2[j]) || !std::isfinite(g->p3[j]))
+                return GLABC_ERR_ARG;
+        return GLABC_OK;
+    }
+    if (g->kind != GLABC_DIST_DIAG_GAUSS && g->kind != GLABC_DIST_UNIFORM) return GLABC_ERR_KIND;
+    for (int j = 0; j < g->dim; ++j) {
+        if (!std::isfinite(g->p0[j]) || !std::isfinite(g->p1[j]) || !std::isfinite(g->p2[j])) return GLABC_ERR_ARG;
+        if (g->kind == GLABC_DIST_DIAG_GAUSS && !(g->p2[j] > 0.0f)) return GLABC_ERR_ARG;
+    }
+    return std::isfinite(g->c0) ? GLABC_OK : GLABC_ERR_ARG;
+}
+
+// allow_user_sim: the row-wise callbacks, where the simulator is not involved
+inline int check_model(const glabc_model* m, bool allow_user_sim = false, bool allow_gamma_prior = false)
+{
+    if (!m) return GLABC_ERR_NULL;
+    const bool user = allow_user_sim && m->sim_kind == GLABC_SIM_USER;
+    if (!user && m->sim_kind != GLABC_SIM_ABS_GAUSS && m->sim_kind != GLABC_SIM_GK) return GLABC_ERR_KIND;
+    if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    int rc = check_dist(&m->prior, m->theta_dim, allow_gamma_prior);
+    if (rc) return rc;
+    if (user) {
+        // neither gk_c nor the noise descriptor is read
+    } else if (m->sim_kind == GLABC_SIM_GK) {
+        if (m->theta_dim != 4 || m->y_dim != 8) return GLABC_ERR_DIM;          // the compiled g-and-k shape
+        if (!std::isfinite(m->gk_c)) return GLABC_ERR_ARG;
+    } else {
+        if (m->y_dim != m->theta_dim) return GLABC_ERR_DIM;
+        rc = check_dist(&m->noise, m->y_dim);
+        if (rc) return rc;
+        if (m->noise.kind != GLABC_DIST_DIAG_GAUSS) return GLABC_ERR_KIND;
+    }
+    if (!std::isfinite(m->kern_log_scale) || !(m->kern_scale > 0.0f) || !std::isfinite(m->kern_scale) ||
+        !std::isfinite(m->kern_c0))
+        return GLABC_ERR_ARG;
+    for (int j = 0; j < m->y_dim; ++j)
+        if (!std::isfinite(m->y_obs[j])) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
+// ---- glabc_chains ------------------------------------------------------------------------------------------------------
+// the arrays an algorithm reads: theta and y always, log_w and flags for iSIR, the float64 state and flags for GLMALA
+enum ChainForm { CHAINS_PLAIN = 0, CHAINS_ISIR = 1, CHAINS_MALA = 2 };
+
+inline int check_chain_pointers(const glabc_chains* c, ChainForm form)
+{
+    if (!c || !c->theta || !c->y) return GLABC_ERR_NULL;
+    if (form == CHAINS_ISIR && (!c->log_w || !c->flags)) return GLABC_ERR_NULL;
+    if (form == CHAINS_MALA && (!c->flags || !c->theta64 || !c->y64 || !c->log_w64 || !c->grad)) return GLABC_ERR_NULL;
+    return GLABC_OK;
+}
+
+inline int check_chain_range(const glabc_chains* c)
+{
+    return (c->n_chains < 0 || c->stride < c->n_chains || c->chain0 < 0) ? GLABC_ERR_ARG : GLABC_OK;
+}
+
+inline int check_chains(const glabc_chains* c, ChainForm form)
+{
+    const int rc = check_chain_pointers(c, form);
+    return rc ? rc : check_chain_range(c);
+}
+
+// ---- glabc_run: what every stepping entry point asks ---------------------------------------------------------------------
+inline int check_frequency(const glabc_run* r)
+{
+    return (!(r->global_frequency >= 0.0f) && !(r->global_frequency < 0.0f)) ? GLABC_ERR_ARG : GLABC_OK;      // NaN
+}
+
+inline int check_history(const glabc_run* r, int64_t n_chains)
+{
+    return (r->history && r->hist_stride < n_chains) ? GLABC_ERR_ARG : GLABC_OK;
+}
+
+inline int check_moments(const glabc_run* r)
+{
+    return (r->moments && (!r->moments->sum_theta || !r->moments->sum_outer || !r->moments->sum_jump)) ? GLABC_ERR_NULL : GLABC_OK;
+}
+
+// the Philox step counter is 32 bits wide
+inline int check_step_counter(const glabc_run* r)
+{
+    return ((uint64_t)r->step0 + (uint64_t)r->n_steps > 0xFFFFFFFFull) ? GLABC_ERR_ARG : GLABC_OK;
+}
+
+// lanes_per_chain, 0 = the library chooses: the lane-group kernel (batch sizes > GLABC_MAX_BATCH) and the register kernels
+inline int check_lanes_wide(int lanes)
+{
+    return (lanes == 0 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64) ? GLABC_OK : GLABC_ERR_ARG;
+}
+
+inline int check_lanes(int lanes) { return (lanes == 0 || lanes == 1 || lanes == 2 || lanes == 4) ? GLABC_OK : GLABC_ERR_ARG; }
+
+}  // namespace glabc

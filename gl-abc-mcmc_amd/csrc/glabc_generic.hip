@@ -23,7 +23,9 @@
 #include <cstdint>
 #include <cstring>
 
+#include "glabc_check.h"
 #include "glabc_device.h"
+#include "glabc_launch.h"
 
 namespace glabc {
 
@@ -412,31 +414,24 @@ __global__ void __launch_bounds__(64) rowsum_kernel(const float* __restrict__ x,
 // =================================================================================================
 using namespace glabc;
 
-static int finish() { return hipGetLastError() == hipSuccess ? GLABC_OK : GLABC_ERR_LAUNCH; }
-
-// allow_gamma: the global / importance proposal may be a Gamma (include/glabc.h); the local increment may not
+// a proposal the caller supplies (null: it draws or scores that part itself), checked by check_dist (glabc_check.h);
+// allow_gamma: the global / importance proposal may be a Gamma (include/glabc.h), the local increment may not
 static int pack_gen_dist(const glabc_dist* g, int dim, GenDist* o, bool allow_gamma)
 {
     std::memset(o, 0, sizeof *o);
     if (!g) return GLABC_OK;
-    if (g->dim != dim || dim < 1 || dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    if (int e = check_dist(g, dim, allow_gamma)) return e;
     const bool gamma = g->kind == GLABC_DIST_GAMMA;
-    if (g->kind != GLABC_DIST_DIAG_GAUSS && g->kind != GLABC_DIST_UNIFORM && !(gamma && allow_gamma)) return GLABC_ERR_KIND;
     o->present = 1;
     o->kind = g->kind;
     o->dim = g->dim;
     o->c0 = gamma ? 0.0f : g->c0;
-    if (!gamma && !std::isfinite(g->c0)) return GLABC_ERR_ARG;
     for (int j = 0; j < GLABC_MAX_DIM; ++j) {
         const bool in = j < dim;
         o->p0[j] = in ? g->p0[j] : 0.0f;
         o->p1[j] = in ? g->p1[j] : 0.0f;
         o->p2[j] = in ? g->p2[j] : 1.0f;
         o->p3[j] = (in && gamma) ? g->p3[j] : 0.0f;
-        if (in && (!std::isfinite(g->p0[j]) || !std::isfinite(g->p1[j]) || !std::isfinite(g->p2[j]))) return GLABC_ERR_ARG;
-        if (in && g->kind == GLABC_DIST_DIAG_GAUSS && !(g->p2[j] > 0.0f)) return GLABC_ERR_ARG;
-        if (in && gamma && (!(g->p0[j] > 0.0f) || !(g->p1[j] > 0.0f) || !(g->p2[j] > 0.0f) || !std::isfinite(g->p3[j])))
-            return GLABC_ERR_ARG;                                       // shape, rate, scale > 0; gammaln(shape) finite
     }
     return GLABC_OK;
 }
@@ -450,9 +445,9 @@ static int pack_common(int algo, const glabc_dist* local, const glabc_dist* glob
     if (io->n_prop < 1 || (algo == GLABC_ALGO_GLOBALMCMC && io->n_prop != 1)) return GLABC_ERR_ARG;
     if ((int64_t)io->n_prop * c->n_chains > (int64_t)1 << 40) return GLABC_ERR_ARG;
     if (r->n_steps != 1 || r->tape || r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
-    if (c->n_chains < 0 || c->stride < c->n_chains || c->chain0 < 0) return GLABC_ERR_ARG;
-    if (!c->theta || !c->y) return GLABC_ERR_NULL;
-    if (!(r->global_frequency >= 0.0f) && !(r->global_frequency < 0.0f)) return GLABC_ERR_ARG;
+    if (int e = check_chain_range(c)) return e;
+    if (int e = check_chain_pointers(c, CHAINS_PLAIN)) return e;
+    if (int e = check_frequency(r)) return e;
     std::memset(a, 0, sizeof *a);
     int rc = pack_gen_dist(local, io->theta_dim, &a->local, false);
     if (rc) return rc;
@@ -479,9 +474,9 @@ static int pack_common(int algo, const glabc_dist* local, const glabc_dist* glob
     a->gf_chain = r->global_frequency_per_chain;
     a->history = r->history;
     a->hist_stride = r->hist_stride;
-    if (r->history && r->hist_stride < c->n_chains) return GLABC_ERR_ARG;
+    if (int e = check_history(r, c->n_chains)) return e;
+    if (int e = check_moments(r)) return e;
     if (r->moments) {
-        if (!r->moments->sum_theta || !r->moments->sum_outer || !r->moments->sum_jump) return GLABC_ERR_NULL;
         a->sum_theta = r->moments->sum_theta;
         a->sum_outer = r->moments->sum_outer;
         a->sum_jump = r->moments->sum_jump;
@@ -502,8 +497,6 @@ static int pack_common(int algo, const glabc_dist* local, const glabc_dist* glob
     return GLABC_OK;
 }
 
-static unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 extern "C" {
 
 __attribute__((visibility("default"))) int glabc_propose(int algo, const glabc_dist* local, const glabc_dist* global,
@@ -517,8 +510,8 @@ __attribute__((visibility("default"))) int glabc_propose(int algo, const glabc_d
     if ((local || global) && io->theta_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
     if (io->noise_dim > 0 && !io->sim_noise) return GLABC_ERR_NULL;
     if (chains->n_chains == 0) return GLABC_OK;
-    hipLaunchKernelGGL(propose_kernel, dim3(blocks_for(chains->n_chains * io->n_prop)), dim3(256), 0, (hipStream_t)stream, a);
-    return finish();
+    hipLaunchKernelGGL(propose_kernel, dim3(grid_for(chains->n_chains * io->n_prop, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int glabc_propose_redraw(const glabc_dist* local, const glabc_chains* chains,
@@ -534,8 +527,8 @@ __attribute__((visibility("default"))) int glabc_propose_redraw(const glabc_dist
     if (chains->n_chains == 0) return GLABC_OK;
     a.redraw_round = round;
     a.n_redrawn = n_redrawn;
-    hipLaunchKernelGGL(redraw_kernel, dim3(blocks_for(chains->n_chains)), dim3(256), 0, (hipStream_t)stream, a);
-    return finish();
+    hipLaunchKernelGGL(redraw_kernel, dim3(grid_for(chains->n_chains, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int glabc_select(int algo, const glabc_dist* global, const glabc_chains* chains,
@@ -550,8 +543,8 @@ __attribute__((visibility("default"))) int glabc_select(int algo, const glabc_di
     if (algo != GLABC_ALGO_GLOBALMCMC && (!chains->log_w || !chains->flags)) return GLABC_ERR_NULL;
     if (!global && !io->q_cur) return GLABC_ERR_NULL;                     // someone has to supply q(Theta_old)
     if (chains->n_chains == 0) return GLABC_OK;
-    hipLaunchKernelGGL(select_kernel, dim3(blocks_for(chains->n_chains)), dim3(256), 0, (hipStream_t)stream, a);
-    return finish();
+    hipLaunchKernelGGL(select_kernel, dim3(grid_for(chains->n_chains, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int glabc_selftest_rowsum(const float* x, int32_t n_rows, int32_t n, float* out, void* stream)
@@ -559,8 +552,8 @@ __attribute__((visibility("default"))) int glabc_selftest_rowsum(const float* x,
     if (!x || !out) return GLABC_ERR_NULL;
     if (n_rows < 0 || n < 1) return GLABC_ERR_ARG;
     if (n_rows == 0) return GLABC_OK;
-    hipLaunchKernelGGL(rowsum_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, (hipStream_t)stream, x, n_rows, n, out);
-    return finish();
+    hipLaunchKernelGGL(rowsum_kernel, dim3(grid_for(n_rows, 64)), dim3(64), 0, (hipStream_t)stream, x, n_rows, n, out);
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int glabc_model_simulate(const glabc_model* m, const float* theta, const float* eps,
@@ -590,8 +583,8 @@ __attribute__((visibility("default"))) int glabc_model_simulate(const glabc_mode
     s.row0 = row0;
     s.seed_lo = (uint32_t)seed;
     s.seed_hi = (uint32_t)(seed >> 32);
-    hipLaunchKernelGGL(simulate_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, s);
-    return finish();
+    hipLaunchKernelGGL(simulate_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, s);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -18,6 +18,9 @@
 #include <cstring>
 #include <mutex>
 
+#include "glabc_check.h"
+#include "glabc_dispatch.h"
+#include "glabc_launch.h"
 #include "glabc_mala.h"
 #include "glabc_pack.h"
 #include "glabc_plan.h"
@@ -498,71 +501,6 @@ __global__ void __launch_bounds__(256) gamma_log_prob_kernel(const GammaArgs a)
 // =================================================================================================
 using namespace glabc;
 
-static thread_local int g_last_hip_error = 0;
-
-static bool finite_dist(const glabc_dist* g)
-{
-    for (int j = 0; j < g->dim; ++j)
-        if (!std::isfinite(g->p0[j]) || !std::isfinite(g->p1[j]) || !std::isfinite(g->p2[j])) return false;
-    return std::isfinite(g->c0);
-}
-
-// allow_gamma: GLABC_DIST_GAMMA is known where include/glabc.h says so (importance / global proposal and prior of
-// glabc_glmcmc_steps / glabc_globalmcmc_steps / glabc_init_weights, glabc_dist_log_prob, the row-wise Model callbacks)
-static int check_dist(const glabc_dist* g, int dim, bool allow_gamma = false)
-{
-    if (!g) return GLABC_ERR_NULL;
-    if (g->dim < 1 || g->dim > GLABC_MAX_DIM || (dim > 0 && g->dim != dim)) return GLABC_ERR_DIM;
-    if (g->kind == GLABC_DIST_GAMMA) {
-        if (!allow_gamma) return GLABC_ERR_KIND;
-        for (int j = 0; j < g->dim; ++j)            // shape, rate, scale = 1/rate > 0 and finite; gammaln(shape) finite
-            if (!(g->p0[j] > 0.0f) || !std::isfinite(g->p0[j]) || !(g->p1[j] > 0.0f) || !std::isfinite(g->p1[j]) ||
-                !(g->p2[j] > 0.0f) || !std::isfinite(g->p2[j]) || !std::isfinite(g->p3[j]))
-                return GLABC_ERR_ARG;
-        return GLABC_OK;
-    }
-    if (g->kind != GLABC_DIST_DIAG_GAUSS && g->kind != GLABC_DIST_UNIFORM) return GLABC_ERR_KIND;
-    if (!finite_dist(g)) return GLABC_ERR_ARG;
-    if (g->kind == GLABC_DIST_DIAG_GAUSS)
-        for (int j = 0; j < g->dim; ++j)
-            if (!(g->p2[j] > 0.0f)) return GLABC_ERR_ARG;
-    return GLABC_OK;
-}
-
-static int check_model(const glabc_model* m, bool allow_user_sim = false, bool allow_gamma_prior = false)
-{
-    if (!m) return GLABC_ERR_NULL;
-    if (allow_user_sim && m->sim_kind == GLABC_SIM_USER) {            // row-wise callbacks: the simulator is not involved
-        if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
-        int rc0 = check_dist(&m->prior, m->theta_dim, allow_gamma_prior);
-        if (rc0) return rc0;
-        if (!std::isfinite(m->kern_log_scale) || !(m->kern_scale > 0.0f) || !std::isfinite(m->kern_scale) || !std::isfinite(m->kern_c0))
-            return GLABC_ERR_ARG;
-        for (int j = 0; j < m->y_dim; ++j)
-            if (!std::isfinite(m->y_obs[j])) return GLABC_ERR_ARG;
-        return GLABC_OK;
-    }
-    if (m->sim_kind != GLABC_SIM_ABS_GAUSS && m->sim_kind != GLABC_SIM_GK) return GLABC_ERR_KIND;
-    if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
-    int rc = check_dist(&m->prior, m->theta_dim, allow_gamma_prior);
-    if (rc) return rc;
-    if (m->sim_kind == GLABC_SIM_GK) {
-        if (m->theta_dim != 4 || m->y_dim != 8) return GLABC_ERR_DIM;          // the compiled g-and-k shape
-        if (!std::isfinite(m->gk_c)) return GLABC_ERR_ARG;
-    } else {
-        if (m->y_dim != m->theta_dim) return GLABC_ERR_DIM;
-        rc = check_dist(&m->noise, m->y_dim);
-        if (rc) return rc;
-        if (m->noise.kind != GLABC_DIST_DIAG_GAUSS) return GLABC_ERR_KIND;
-    }
-    if (!std::isfinite(m->kern_log_scale) || !(m->kern_scale > 0.0f) || !std::isfinite(m->kern_scale) ||
-        !std::isfinite(m->kern_c0))
-        return GLABC_ERR_ARG;
-    for (int j = 0; j < m->y_dim; ++j)
-        if (!std::isfinite(m->y_obs[j])) return GLABC_ERR_ARG;
-    return GLABC_OK;
-}
-
 // RN(1/s) if the three-instruction division of model_log_kernel is exact for this divisor, else 0.  The check runs the
 // device's instruction sequence (IEEE mul + two fused multiply-adds) over all 2^23 significands of the dividend and
 // compares with the IEEE quotient (~7 ms, remembered per divisor); powers of two scale every step exactly.
@@ -579,6 +517,8 @@ __attribute__((target("fma"))) static bool reciprocal_division_exact(float s, fl
 }
 
 namespace glabc {
+thread_local int g_last_hip_error = 0;          // glabc_launch.h: what glabc_last_hip_error() reports
+
 float verified_reciprocal(float s)
 {
     if (!(s >= 0x1p-20f && s <= 0x1p20f) || !__builtin_cpu_supports("fma")) return 0.0f;
@@ -606,18 +546,6 @@ static StepArgs<D, YD> pack_args(const glabc_model* m, const glabc_dist* local, 
                                  (local && YD == D) ? verified_reciprocal(m->kern_scale) : 0.0f);      // sampler launches only
 }
 
-static int finish_launch()
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return GLABC_ERR_LAUNCH;
-    }
-    return GLABC_OK;
-}
-
-static unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 static int check_run(const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
                      const glabc_run* r, bool isir)
 {
@@ -631,26 +559,23 @@ static int check_run(const glabc_model* m, const glabc_dist* local, const glabc_
     if (gamma && (m->sim_kind != GLABC_SIM_ABS_GAUSS || m->theta_dim > 4)) return GLABC_ERR_KIND;    // the instantiated Gamma variants
     if (gamma && r && r->tape) return GLABC_ERR_ARG;                // a tape has no Gamma variates
     if (!c || !r) return GLABC_ERR_NULL;
-    if (!c->theta || !c->y) return GLABC_ERR_NULL;
-    if (isir && (!c->log_w || !c->flags)) return GLABC_ERR_NULL;
-    if (c->n_chains < 0 || c->stride < c->n_chains || c->chain0 < 0) return GLABC_ERR_ARG;
+    if (int e = check_chains(c, isir ? CHAINS_ISIR : CHAINS_PLAIN)) return e;
     if (r->n_steps < 0) return GLABC_ERR_ARG;
-    if (!(r->global_frequency >= 0.0f) && !(r->global_frequency < 0.0f)) return GLABC_ERR_ARG;    // NaN
+    if (int e = check_frequency(r)) return e;
     if (isir && (r->batch_size < 1 || r->batch_size > GLABC_MAX_BATCH_WIDE)) return GLABC_ERR_ARG;
     if (isir && r->batch_size > GLABC_MAX_BATCH) {               // the wide kernel: 8..64 lanes per chain, Philox only
         if (r->tape) return GLABC_ERR_ARG;
-        if (r->lanes_per_chain != 0 && r->lanes_per_chain != 8 && r->lanes_per_chain != 16 && r->lanes_per_chain != 32 &&
-            r->lanes_per_chain != 64)
-            return GLABC_ERR_ARG;
-    } else if (r->lanes_per_chain != 0 && r->lanes_per_chain != 1 && r->lanes_per_chain != 2 && r->lanes_per_chain != 4)
-        return GLABC_ERR_ARG;
-    if (r->history && r->hist_stride < c->n_chains) return GLABC_ERR_ARG;
-    if (r->moments && (!r->moments->sum_theta || !r->moments->sum_outer || !r->moments->sum_jump)) return GLABC_ERR_NULL;
+        if (int e = check_lanes_wide(r->lanes_per_chain)) return e;
+    } else if (int e = check_lanes(r->lanes_per_chain)) {
+        return e;
+    }
+    if (int e = check_history(r, c->n_chains)) return e;
+    if (int e = check_moments(r)) return e;
     if (r->tape) {                           // replayed random numbers: device arrays covering exactly this call
         if (!r->tape->u || !r->tape->z || (isir && !r->tape->r)) return GLABC_ERR_NULL;
         if (r->tape->n_prop < 1 || (isir && r->tape->n_prop < r->batch_size)) return GLABC_ERR_ARG;
     }
-    if ((uint64_t)r->step0 + (uint64_t)r->n_steps > 0xFFFFFFFFull) return GLABC_ERR_ARG;
+    if (int e = check_step_counter(r)) return e;
     if (r->step0_device) return GLABC_ERR_ARG;                  // the split-phase entry points only
     if (r->math_mode != GLABC_MATH_EXACT && r->math_mode != GLABC_MATH_FAST) return GLABC_ERR_ARG;
     if (r->math_mode == GLABC_MATH_FAST) {                      // the opt-in variant: where a team kernel exists (include/glabc.h)
@@ -731,21 +656,16 @@ static int run_sampler(int algo, const glabc_model* m, const glabc_dist* local, 
     const LaunchPlan plan = plan_launch(in);
     if (plan.kind == PLAN_REFUSED) return plan.status;
     hipStream_t s = (hipStream_t)stream;
-    switch (in.gk ? 0 : m->theta_dim) {
-#define GLABC_DIM_CASE(d) case d: rc = launch_planned<d, d>(plan, algo, r, pack_args<d>(m, local, global, c, r), s); break;
-    case 0: rc = launch_planned<4, 8>(plan, algo, r, pack_args<4, 8>(m, local, global, c, r), s); break;      // g-and-k
-        GLABC_DIM_CASE(1) GLABC_DIM_CASE(2) GLABC_DIM_CASE(3) GLABC_DIM_CASE(4)
-        GLABC_DIM_CASE(5) GLABC_DIM_CASE(6) GLABC_DIM_CASE(7) GLABC_DIM_CASE(8)
-#undef GLABC_DIM_CASE
-    default: return GLABC_ERR_DIM;
-    }
-    if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();
-    return rc;
+    if (in.gk) return launch_planned<4, 8>(plan, algo, r, pack_args<4, 8>(m, local, global, c, r), s);      // g-and-k
+    return dispatch_range<1, 8>(m->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return launch_planned<D, D>(plan, algo, r, pack_args<D>(m, local, global, c, r), s);
+    });
 }
 
 template <int D>
 static MalaArgs<D> pack_mala(const glabc_model* m, const glabc_dist* imp, const glabc_mala* p, const glabc_chains* c,
-                             const glabc_run* r, int credit, int prio)
+                             const glabc_run* r, const Tuning& tune)
 {
     MalaArgs<D> a;
     std::memset(&a, 0, sizeof a);
@@ -765,17 +685,9 @@ static MalaArgs<D> pack_mala(const glabc_model* m, const glabc_dist* imp, const 
     // fills the issue slots it leaves (37.9 against 43.9 ms per 2000 iterations of 65 536 chains) -- and takes the same share of
     // the gradient items as a helper lane (credit 0; measured optimum, flat between -2 and +2).  GLABC_MALA_PRIO /
     // GLABC_MALA_CREDIT override both for tuning runs (read_tuning)
-    a.credit = credit;
-    a.prio = prio;
+    a.credit = tune.mala_credit;
+    a.prio = tune.mala_prio;
     return a;
-}
-
-static int check_mala_chains(const glabc_chains* c)
-{
-    if (!c) return GLABC_ERR_NULL;
-    if (!c->theta || !c->y || !c->flags || !c->theta64 || !c->y64 || !c->log_w64 || !c->grad) return GLABC_ERR_NULL;
-    if (c->n_chains < 0 || c->stride < c->n_chains || c->chain0 < 0) return GLABC_ERR_ARG;
-    return GLABC_OK;
 }
 
 extern "C" {
@@ -790,51 +702,39 @@ __attribute__((visibility("default"))) int glabc_glmala_steps(const glabc_model*
     rc = check_dist(importance, model->theta_dim);
     if (rc) return rc;
     if (!mala || !r) return GLABC_ERR_NULL;
-    rc = check_mala_chains(c);
-    if (rc) return rc;
+    if (int e = check_chains(c, CHAINS_MALA)) return e;
     if (r->n_steps < 0 || r->batch_size < 1 || r->batch_size > GLABC_MAX_BATCH) return GLABC_ERR_ARG;
-    if (!(r->global_frequency >= 0.0f) && !(r->global_frequency < 0.0f)) return GLABC_ERR_ARG;
+    if (int e = check_frequency(r)) return e;
     if (r->global_frequency_per_chain) return GLABC_ERR_ARG;        // GLMCMC / GlobalMCMC only
     if (mala->num_grad < 2 || mala->num_grad > (1 << 16) || !(mala->tau > 0.0) || !std::isfinite(mala->tau) ||
         !std::isfinite(mala->tau_sq) || !std::isfinite(mala->eps_sq) || !(mala->eps_sq >= 0.0))
         return GLABC_ERR_ARG;
-    if (r->history && r->hist_stride < c->n_chains) return GLABC_ERR_ARG;
-    if (r->moments && (!r->moments->sum_theta || !r->moments->sum_outer || !r->moments->sum_jump)) return GLABC_ERR_NULL;
+    if (int e = check_history(r, c->n_chains)) return e;
+    if (int e = check_moments(r)) return e;
     if (r->tape || r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
     if (r->lanes_per_chain < 0 || r->lanes_per_chain > 2) return GLABC_ERR_ARG;      // wavefronts per 64 chains (theta_dim 2)
-    if ((uint64_t)r->step0 + (uint64_t)r->n_steps > 0xFFFFFFFFull) return GLABC_ERR_ARG;
+    if (int e = check_step_counter(r)) return e;
     if (c->n_chains == 0 || r->n_steps == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
     const Tuning tune = read_tuning();
-    switch (model->theta_dim) {
-    case 1: rc = launch_glmala_dim<1>(r->batch_size, pack_mala<1>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
-    case 2: rc = launch_glmala_dim<2>(r->batch_size, pack_mala<2>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
-    case 3: rc = launch_glmala_dim<3>(r->batch_size, pack_mala<3>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
-    case 4: rc = launch_glmala_dim<4>(r->batch_size, pack_mala<4>(model, importance, mala, c, r, tune.mala_credit, tune.mala_prio), s); break;
-    default: return GLABC_ERR_DIM;
-    }
-    if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();
-    return rc;
+    return dispatch_range<1, 4>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return launch_glmala_dim<D>(r->batch_size, pack_mala<D>(model, importance, mala, c, r, tune), s);
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_glmala_init(const glabc_model* model, const glabc_chains* c, void* stream)
 {
     int rc = check_model(model);
     if (rc) return rc;
-    rc = check_mala_chains(c);
-    if (rc) return rc;
+    if (int e = check_chains(c, CHAINS_MALA)) return e;
     if (c->n_chains == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
     const Tuning tune = read_tuning();
-    switch (model->theta_dim) {
-    case 1: rc = launch_glmala_init_dim<1>(pack_mala<1>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
-    case 2: rc = launch_glmala_init_dim<2>(pack_mala<2>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
-    case 3: rc = launch_glmala_init_dim<3>(pack_mala<3>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
-    case 4: rc = launch_glmala_init_dim<4>(pack_mala<4>(model, nullptr, nullptr, c, nullptr, tune.mala_credit, tune.mala_prio), s); break;
-    default: return GLABC_ERR_DIM;
-    }
-    if (rc == GLABC_ERR_LAUNCH) g_last_hip_error = (int)hipPeekAtLastError();
-    return rc;
+    return dispatch_range<1, 4>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return launch_glmala_init_dim<D>(pack_mala<D>(model, nullptr, nullptr, c, nullptr, tune), s);
+    });
 }
 
 }  // extern "C"
@@ -843,21 +743,17 @@ template <int D>
 static int launch_pool_weights(const PoolArgs<D>& p, hipStream_t s)
 {
     hipLaunchKernelGGL((pool_weights_kernel<D>), dim3(grid_for(p.n_rows, 256)), dim3(256), 0, s, p);
-    return finish_launch();
+    return launch_status();
 }
 
 template <int D>
 static int launch_nf_step(const PoolArgs<D>& p, int N, hipStream_t s)
 {
     dim3 grid(grid_for(p.s.n_chains, 64)), block(64);
-    switch (N) {
-#define GLABC_CASE(n) case n: hipLaunchKernelGGL((nf_step_kernel<D, n>), grid, block, 0, s, p); break;
-        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
-        GLABC_CASE(9) GLABC_CASE(10) GLABC_CASE(11) GLABC_CASE(12) GLABC_CASE(13) GLABC_CASE(14) GLABC_CASE(15) GLABC_CASE(16)
-#undef GLABC_CASE
-    default: return GLABC_ERR_ARG;
-    }
-    return finish_launch();
+    return dispatch_range<1, 16>(N, GLABC_ERR_ARG, [&](auto n) {
+        hipLaunchKernelGGL((nf_step_kernel<D, decltype(n)::value>), grid, block, 0, s, p);
+        return launch_status();
+    });
 }
 
 extern "C" {
@@ -878,20 +774,15 @@ __attribute__((visibility("default"))) int glabc_pool_weights(const glabc_model*
     std::memset(&r, 0, sizeof r);
     r.seed = seed;
     hipStream_t s = (hipStream_t)stream;
-#define GLABC_POOLW(d)                                                        \
-    case d: {                                                                 \
-        PoolArgs<d> p;                                                        \
-        std::memset(&p, 0, sizeof p);                                         \
-        p.s = pack_args<d>(model, nullptr, &model->prior, &dummy, &r);        \
-        p.theta = theta; p.log_q = log_q; p.x_out = x_out; p.w_out = w_out;   \
-        p.n_rows = n_rows; p.row_id0 = row_id0;                               \
-        return launch_pool_weights<d>(p, s);                                  \
-    }
-    switch (model->theta_dim) {
-        GLABC_POOLW(1) GLABC_POOLW(2) GLABC_POOLW(3) GLABC_POOLW(4)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_POOLW
+    return dispatch_range<1, 4>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        PoolArgs<D> p;
+        std::memset(&p, 0, sizeof p);
+        p.s = pack_args<D>(model, nullptr, &model->prior, &dummy, &r);
+        p.theta = theta; p.log_q = log_q; p.x_out = x_out; p.w_out = w_out;
+        p.n_rows = n_rows; p.row_id0 = row_id0;
+        return launch_pool_weights<D>(p, s);
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_dist_forward(const glabc_dist* dist, int64_t n, uint64_t seed, int64_t row0,
@@ -904,21 +795,16 @@ __attribute__((visibility("default"))) int glabc_dist_forward(const glabc_dist* 
     if (n == 0) return GLABC_OK;
     if (!z_out || !log_p_out) return GLABC_ERR_NULL;
     hipStream_t s = (hipStream_t)stream;
-#define GLABC_FWD(d)                                                          \
-    case d: {                                                                 \
-        ForwardArgs<d> a;                                                     \
-        std::memset(&a, 0, sizeof a);                                         \
-        a.g = pack_dist<d>(dist);                                             \
-        a.n = n; a.row0 = row0; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); \
-        a.z = z_out; a.log_p = log_p_out;                                     \
-        hipLaunchKernelGGL((dist_forward_kernel<d>), dim3(grid_for(n, 256)), dim3(256), 0, s, a); \
-        return finish_launch();                                               \
-    }
-    switch (dist->dim) {
-        GLABC_FWD(1) GLABC_FWD(2) GLABC_FWD(3) GLABC_FWD(4) GLABC_FWD(5) GLABC_FWD(6) GLABC_FWD(7) GLABC_FWD(8)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_FWD
+    return dispatch_range<1, 8>(dist->dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        ForwardArgs<D> a;
+        std::memset(&a, 0, sizeof a);
+        a.g = pack_dist<D>(dist);
+        a.n = n; a.row0 = row0; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+        a.z = z_out; a.log_p = log_p_out;
+        hipLaunchKernelGGL((dist_forward_kernel<D>), dim3(grid_for(n, 256)), dim3(256), 0, s, a);
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_kde_train_weights(const glabc_model* model, const float* theta, const float* dis,
@@ -934,21 +820,16 @@ __attribute__((visibility("default"))) int glabc_kde_train_weights(const glabc_m
     glabc_run r;
     std::memset(&r, 0, sizeof r);
     hipStream_t s = (hipStream_t)stream;
-#define GLABC_TRAINW(d)                                                       \
-    case d: {                                                                 \
-        PoolArgs<d> p;                                                        \
-        std::memset(&p, 0, sizeof p);                                         \
-        p.s = pack_args<d>(model, nullptr, &model->prior, &dummy, &r);        \
-        p.theta = theta; p.x = dis; p.log_q = log_q; p.w_out = w_out;         \
-        p.n_rows = n;                                                         \
-        hipLaunchKernelGGL((train_weights_kernel<d>), dim3(grid_for(n, 256)), dim3(256), 0, s, p); \
-        return finish_launch();                                               \
-    }
-    switch (model->theta_dim) {
-        GLABC_TRAINW(1) GLABC_TRAINW(2) GLABC_TRAINW(3) GLABC_TRAINW(4)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_TRAINW
+    return dispatch_range<1, 4>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        PoolArgs<D> p;
+        std::memset(&p, 0, sizeof p);
+        p.s = pack_args<D>(model, nullptr, &model->prior, &dummy, &r);
+        p.theta = theta; p.x = dis; p.log_q = log_q; p.w_out = w_out;
+        p.n_rows = n;
+        hipLaunchKernelGGL((train_weights_kernel<D>), dim3(grid_for(n, 256)), dim3(256), 0, s, p);
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_glmcmc_nf_step(const glabc_model* model, const glabc_dist* local,
@@ -961,30 +842,26 @@ __attribute__((visibility("default"))) int glabc_glmcmc_nf_step(const glabc_mode
     if (rc) return rc;
     if (model->sim_kind != GLABC_SIM_ABS_GAUSS) return GLABC_ERR_KIND;
     if (!pool || !c || !r) return GLABC_ERR_NULL;
-    if (!pool->theta || !pool->x || !pool->w || !pool->log_q_old || !pool->kk || !c->theta || !c->y) return GLABC_ERR_NULL;
-    if (c->n_chains < 0 || c->stride < c->n_chains || c->chain0 < 0 || pool->step_size < 1) return GLABC_ERR_ARG;
+    if (!pool->theta || !pool->x || !pool->w || !pool->log_q_old || !pool->kk) return GLABC_ERR_NULL;
+    if (int e = check_chains(c, CHAINS_PLAIN)) return e;
+    if (pool->step_size < 1) return GLABC_ERR_ARG;
     if (r->n_steps != 1 || r->batch_size < 1 || r->batch_size > GLABC_MAX_BATCH) return GLABC_ERR_ARG;
-    if (r->history && r->hist_stride < c->n_chains) return GLABC_ERR_ARG;
+    if (int e = check_history(r, c->n_chains)) return e;
     if (r->tape || r->moments || r->global_frequency_per_chain || r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
     if ((pool->moved_idx == nullptr) != (pool->n_moved == nullptr)) return GLABC_ERR_NULL;
     if (c->n_chains > 0x7fffffff) return GLABC_ERR_ARG;
     if (c->n_chains == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
-#define GLABC_NFSTEP(d)                                                       \
-    case d: {                                                                 \
-        PoolArgs<d> p;                                                        \
-        std::memset(&p, 0, sizeof p);                                         \
-        p.s = pack_args<d>(model, local, &model->prior, c, r);                \
-        p.theta = pool->theta; p.x = pool->x; p.w = pool->w; p.log_q = pool->log_q_old; p.kk = pool->kk; \
-        p.step_size = pool->step_size;                                        \
-        p.moved_idx = pool->moved_idx; p.n_moved = pool->n_moved; p.n_moved_reset = pool->n_moved_reset; \
-        return launch_nf_step<d>(p, r->batch_size, s);                        \
-    }
-    switch (model->theta_dim) {
-        GLABC_NFSTEP(1) GLABC_NFSTEP(2) GLABC_NFSTEP(3) GLABC_NFSTEP(4)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_NFSTEP
+    return dispatch_range<1, 4>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        PoolArgs<D> p;
+        std::memset(&p, 0, sizeof p);
+        p.s = pack_args<D>(model, local, &model->prior, c, r);
+        p.theta = pool->theta; p.x = pool->x; p.w = pool->w; p.log_q = pool->log_q_old; p.kk = pool->kk;
+        p.step_size = pool->step_size;
+        p.moved_idx = pool->moved_idx; p.n_moved = pool->n_moved; p.n_moved_reset = pool->n_moved_reset;
+        return launch_nf_step<D>(p, r->batch_size, s);
+    });
 }
 
 }  // extern "C"
@@ -1004,7 +881,7 @@ extern "C" __attribute__((visibility("default"))) int glabc_gamma_log_prob(const
     a.out = out;
     a.n = n;
     hipLaunchKernelGGL(gamma_log_prob_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return finish_launch();
+    return launch_status();
 }
 
 extern "C" __attribute__((visibility("default"))) int glabc_gamma_forward(const glabc_gamma* dist, int64_t n, uint64_t seed,
@@ -1026,20 +903,17 @@ extern "C" __attribute__((visibility("default"))) int glabc_gamma_forward(const 
     a.seed_lo = (uint32_t)seed;
     a.seed_hi = (uint32_t)(seed >> 32);
     hipLaunchKernelGGL(gamma_forward_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return finish_launch();
+    return launch_status();
 }
 
 template <int OP>
 static int launch_rowwise(const RowArgs& a, hipStream_t s)
 {
     dim3 grid(grid_for(a.n, 256)), block(256);
-    switch (a.dim) {
-#define GLABC_CASE(d) case d: hipLaunchKernelGGL((rowwise_kernel<OP, d>), grid, block, 0, s, a); break;
-        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
-#undef GLABC_CASE
-    default: return GLABC_ERR_DIM;
-    }
-    return finish_launch();
+    return dispatch_range<1, 8>(a.dim, GLABC_ERR_DIM, [&](auto d) {
+        hipLaunchKernelGGL((rowwise_kernel<OP, decltype(d)::value>), grid, block, 0, s, a);
+        return launch_status();
+    });
 }
 
 extern "C" {
@@ -1065,27 +939,20 @@ __attribute__((visibility("default"))) int glabc_init_weights(const glabc_model*
     if (rc) return rc;
     rc = check_dist(importance, model->theta_dim, true);
     if (rc) return rc;
-    if (!c || !c->theta || !c->y || !c->log_w || !c->flags) return GLABC_ERR_NULL;
-    if (c->n_chains < 0 || c->stride < c->n_chains) return GLABC_ERR_ARG;
+    if (int e = check_chain_pointers(c, CHAINS_ISIR)) return e;
+    if (c->n_chains < 0 || c->stride < c->n_chains) return GLABC_ERR_ARG;      // chain0 is not read
     if (c->n_chains == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(grid_for(c->n_chains, BLOCK)), block(BLOCK);
     if (model->sim_kind == GLABC_SIM_GK) {
         hipLaunchKernelGGL((init_weights_kernel<4, 8>), grid, block, 0, s, pack_args<4, 8>(model, nullptr, importance, c, nullptr));
-        return finish_launch();
+        return launch_status();
     }
-    switch (model->theta_dim) {
-    case 1: hipLaunchKernelGGL((init_weights_kernel<1, 1>), grid, block, 0, s, pack_args<1>(model, nullptr, importance, c, nullptr)); break;
-    case 2: hipLaunchKernelGGL((init_weights_kernel<2, 2>), grid, block, 0, s, pack_args<2>(model, nullptr, importance, c, nullptr)); break;
-    case 3: hipLaunchKernelGGL((init_weights_kernel<3, 3>), grid, block, 0, s, pack_args<3>(model, nullptr, importance, c, nullptr)); break;
-    case 4: hipLaunchKernelGGL((init_weights_kernel<4, 4>), grid, block, 0, s, pack_args<4>(model, nullptr, importance, c, nullptr)); break;
-    case 5: hipLaunchKernelGGL((init_weights_kernel<5, 5>), grid, block, 0, s, pack_args<5>(model, nullptr, importance, c, nullptr)); break;
-    case 6: hipLaunchKernelGGL((init_weights_kernel<6, 6>), grid, block, 0, s, pack_args<6>(model, nullptr, importance, c, nullptr)); break;
-    case 7: hipLaunchKernelGGL((init_weights_kernel<7, 7>), grid, block, 0, s, pack_args<7>(model, nullptr, importance, c, nullptr)); break;
-    case 8: hipLaunchKernelGGL((init_weights_kernel<8, 8>), grid, block, 0, s, pack_args<8>(model, nullptr, importance, c, nullptr)); break;
-    default: return GLABC_ERR_DIM;
-    }
-    return finish_launch();
+    return dispatch_range<1, 8>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        hipLaunchKernelGGL((init_weights_kernel<D, D>), grid, block, 0, s, pack_args<D>(model, nullptr, importance, c, nullptr));
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_dist_log_prob(const glabc_dist* dist, const float* z, int64_t n, float* out,
@@ -1157,18 +1024,10 @@ __attribute__((visibility("default"))) int glabc_esjd(const float* history, int6
     if (n_chains == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(grid_for(n_chains, BLOCK)), block(BLOCK);
-    switch (theta_dim) {
-    case 1: hipLaunchKernelGGL(esjd_kernel<1>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    case 2: hipLaunchKernelGGL(esjd_kernel<2>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    case 3: hipLaunchKernelGGL(esjd_kernel<3>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    case 4: hipLaunchKernelGGL(esjd_kernel<4>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    case 5: hipLaunchKernelGGL(esjd_kernel<5>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    case 6: hipLaunchKernelGGL(esjd_kernel<6>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    case 7: hipLaunchKernelGGL(esjd_kernel<7>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    case 8: hipLaunchKernelGGL(esjd_kernel<8>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out); break;
-    default: return GLABC_ERR_DIM;
-    }
-    return finish_launch();
+    return dispatch_range<1, 8>(theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        hipLaunchKernelGGL(esjd_kernel<decltype(d)::value>, grid, block, 0, s, history, n_rows, n_chains, stride, esjd_out);
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_moments_esjd(const glabc_moments* moments, int64_t n_steps, int32_t theta_dim,
@@ -1180,18 +1039,10 @@ __attribute__((visibility("default"))) int glabc_moments_esjd(const glabc_moment
     if (n_chains == 0) return GLABC_OK;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(grid_for(n_chains, BLOCK)), block(BLOCK);
-    switch (theta_dim) {
-    case 1: hipLaunchKernelGGL(moments_esjd_kernel<1>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    case 2: hipLaunchKernelGGL(moments_esjd_kernel<2>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    case 3: hipLaunchKernelGGL(moments_esjd_kernel<3>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    case 4: hipLaunchKernelGGL(moments_esjd_kernel<4>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    case 5: hipLaunchKernelGGL(moments_esjd_kernel<5>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    case 6: hipLaunchKernelGGL(moments_esjd_kernel<6>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    case 7: hipLaunchKernelGGL(moments_esjd_kernel<7>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    case 8: hipLaunchKernelGGL(moments_esjd_kernel<8>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out); break;
-    default: return GLABC_ERR_DIM;
-    }
-    return finish_launch();
+    return dispatch_range<1, 8>(theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        hipLaunchKernelGGL(moments_esjd_kernel<decltype(d)::value>, grid, block, 0, s, moments->sum_jump, n_steps, n_chains, stride, esjd_out);
+        return launch_status();
+    });
 }
 
 /* Test hooks: evaluate include/glabc_numerics.h ON THE DEVICE so the tests can require bit equality
@@ -1202,7 +1053,7 @@ __attribute__((visibility("default"))) int glabc_selftest_numerics(int op, const
     if (op < 0 || op > 8 || n < 0) return GLABC_ERR_ARG;
     if (n == 0) return GLABC_OK;
     hipLaunchKernelGGL(numerics_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, op, in, out, n);
-    return finish_launch();
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int glabc_selftest_sqrt(uint32_t first_bits, uint32_t last_bits, uint64_t* mismatches, void* stream)
@@ -1211,7 +1062,7 @@ __attribute__((visibility("default"))) int glabc_selftest_sqrt(uint32_t first_bi
     if (last_bits < first_bits) return GLABC_ERR_ARG;
     hipLaunchKernelGGL(sqrt_check_kernel, dim3(4096), dim3(256), 0, (hipStream_t)stream, first_bits, last_bits,
                        (unsigned long long*)mismatches);
-    return finish_launch();
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int glabc_version(void) { return GLABC_VERSION; }

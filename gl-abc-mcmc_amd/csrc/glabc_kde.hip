@@ -16,6 +16,8 @@
 #include "../../include/glabc.h"
 #include "../../include/glabc_numerics.h"
 #include "glabc_device.h"
+#include "glabc_dispatch.h"
+#include "glabc_launch.h"
 
 using namespace glabc;
 
@@ -252,8 +254,6 @@ KdeArgs<D> kde_pack(const glabc_kde* k)
     return a;
 }
 
-int launched() { return hipGetLastError() == hipSuccess ? GLABC_OK : GLABC_ERR_LAUNCH; }
-
 }  // namespace
 
 extern "C" {
@@ -279,13 +279,10 @@ __attribute__((visibility("default"))) int glabc_kde_fit(const float* x, const f
         return GLABC_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-#define GLABC_CASE(d) case d: hipLaunchKernelGGL((kde_fit_kernel<d>), dim3(1), dim3(256), 0, s, a); break;
-    switch (dim) {
-        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_CASE
-    return launched();
+    return dispatch_range<1, 8>(dim, GLABC_ERR_DIM, [&](auto d) {
+        hipLaunchKernelGGL((kde_fit_kernel<decltype(d)::value>), dim3(1), dim3(256), 0, s, a);
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_kde_log_prob(const glabc_kde* kde, const float* pts, int64_t n_points, float* out,
@@ -298,20 +295,14 @@ __attribute__((visibility("default"))) int glabc_kde_log_prob(const glabc_kde* k
     if (!pts || !out) return GLABC_ERR_NULL;
     if (kde->n_samples > (int64_t)1 << 22) return GLABC_ERR_ARG;         // fixed-point sum headroom: 2^22 terms <= 1
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((n_points + 3) / 4)), block(256);
-#define GLABC_CASE(d)                                                              \
-    case d: {                                                                      \
-        KdeArgs<d> a = kde_pack<d>(kde);                                           \
-        a.pts = pts; a.n_points = n_points; a.out = out; a.pts_stride = n_points;  \
-        hipLaunchKernelGGL((kde_log_prob_kernel<d>), grid, block, 0, s, a);        \
-        break;                                                                     \
-    }
-    switch (kde->dim) {
-        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_CASE
-    return launched();
+    const dim3 grid(grid_for(n_points, 4)), block(256);
+    return dispatch_range<1, 8>(kde->dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        KdeArgs<D> a = kde_pack<D>(kde);
+        a.pts = pts; a.n_points = n_points; a.out = out; a.pts_stride = n_points;
+        hipLaunchKernelGGL((kde_log_prob_kernel<D>), grid, block, 0, s, a);
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_kde_log_prob_indexed(const glabc_kde* kde, const float* pts, int64_t stride,
@@ -325,21 +316,15 @@ __attribute__((visibility("default"))) int glabc_kde_log_prob_indexed(const glab
     if (!pts || !out || !idx || !n_dev) return GLABC_ERR_NULL;
     if (kde->n_samples > (int64_t)1 << 22) return GLABC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((max_points + 3) / 4)), block(256);       // wavefronts past the device-side count leave at once
-#define GLABC_CASE(d)                                                              \
-    case d: {                                                                      \
-        KdeArgs<d> a = kde_pack<d>(kde);                                           \
-        a.pts = pts; a.n_points = max_points; a.out = out; a.pts_stride = stride;  \
-        a.idx = idx; a.n_dev = n_dev;                                              \
-        hipLaunchKernelGGL((kde_log_prob_kernel<d>), grid, block, 0, s, a);        \
-        break;                                                                     \
-    }
-    switch (kde->dim) {
-        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_CASE
-    return launched();
+    const dim3 grid(grid_for(max_points, 4)), block(256);      // wavefronts past the device-side count leave at once
+    return dispatch_range<1, 8>(kde->dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        KdeArgs<D> a = kde_pack<D>(kde);
+        a.pts = pts; a.n_points = max_points; a.out = out; a.pts_stride = stride;
+        a.idx = idx; a.n_dev = n_dev;
+        hipLaunchKernelGGL((kde_log_prob_kernel<D>), grid, block, 0, s, a);
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_kde_sample(const glabc_kde* kde, int64_t n, uint64_t seed, int64_t row0, float* out,
@@ -351,21 +336,15 @@ __attribute__((visibility("default"))) int glabc_kde_sample(const glabc_kde* kde
     if (n == 0) return GLABC_OK;
     if (!out || !kde->cum_q) return GLABC_ERR_NULL;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define GLABC_CASE(d)                                                              \
-    case d: {                                                                      \
-        KdeArgs<d> a = kde_pack<d>(kde);                                           \
-        a.n_points = n; a.out = out; a.row0 = row0;                                \
-        a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);            \
-        hipLaunchKernelGGL((kde_sample_kernel<d>), grid, block, 0, s, a);          \
-        break;                                                                     \
-    }
-    switch (kde->dim) {
-        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
-    default: return GLABC_ERR_DIM;
-    }
-#undef GLABC_CASE
-    return launched();
+    const dim3 grid(grid_for(n, 256)), block(256);
+    return dispatch_range<1, 8>(kde->dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        KdeArgs<D> a = kde_pack<D>(kde);
+        a.n_points = n; a.out = out; a.row0 = row0;
+        a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+        hipLaunchKernelGGL((kde_sample_kernel<D>), grid, block, 0, s, a);
+        return launch_status();
+    });
 }
 
 }  // extern "C"

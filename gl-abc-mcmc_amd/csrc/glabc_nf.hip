@@ -31,6 +31,7 @@
 
 #include "../../include/glabc.h"
 #include "../../include/glabc_numerics.h"
+#include "glabc_launch.h"
 #include "glabc_lds_grant.h"
 #include "glabc_nf_layout.h"
 
@@ -757,7 +758,7 @@ static int nf_launch_mode(NfArgs a, int rows_per_wg, int slots_per_wave, hipStre
     if (!grant_dynamic_lds(grant, (const void*)nf_kernel<INV, TILE>, lds_bytes, 0)) return GLABC_ERR_LAUNCH;
     const unsigned grid = (unsigned)((a.n_rows + rows_per_wg - 1) / rows_per_wg);
     hipLaunchKernelGGL((nf_kernel<INV, TILE>), dim3(grid), dim3(64 * NF_WAVES), lds_bytes, s, a);
-    return hipGetLastError() == hipSuccess ? GLABC_OK : GLABC_ERR_LAUNCH;
+    return launch_status();
 }
 
 // Rows per workgroup: the rows are spread over (a multiple of) the 256 CUs in 64-row pairs, one workgroup per CU,

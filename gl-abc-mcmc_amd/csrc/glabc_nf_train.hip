@@ -44,6 +44,7 @@
 
 #include "../../include/glabc.h"
 #include "../../include/glabc_numerics.h"
+#include "glabc_launch.h"
 #include "glabc_lds_grant.h"
 #include "glabc_nf_layout.h"
 
@@ -825,8 +826,8 @@ __attribute__((visibility("default"))) int glabc_nf_grad(const glabc_flow* flow,
     r.n_base_blocks = BASE_BLOCKS;
     r.gl = gl;
     r.n_rows = (double)n_rows;
-    hipLaunchKernelGGL(nf_grad_reduce_kernel, dim3((unsigned)((r.total + 255) / 256)), dim3(256), 0, s, r);
-    return hipGetLastError() == hipSuccess ? GLABC_OK : GLABC_ERR_LAUNCH;
+    hipLaunchKernelGGL(nf_grad_reduce_kernel, dim3(grid_for(r.total, 256)), dim3(256), 0, s, r);
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int glabc_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -852,8 +853,8 @@ __attribute__((visibility("default"))) int glabc_adam_step(float* params, const 
     a.weight_decay = (float)weight_decay;
     a.step_size = (float)(lr / (1.0 - std::pow(beta1, (double)step)));
     a.bias2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? GLABC_OK : GLABC_ERR_LAUNCH;
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(count, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // glabc_sampler_dim.hip -- instantiates sampler_kernel for ONE theta_dim (-DGLABC_DIM=d):
 // GLMCMC for batch sizes 1..GLABC_MAX_BATCH x lanes-per-chain {1,2,4}, GlobalMCMC (one lane).
+#include "glabc_dispatch.h"
+#include "glabc_launch.h"
 #include "glabc_pack.h"
 #include "glabc_sampler.h"
 
@@ -19,7 +21,7 @@ template <int ALGO, int D, int YD, int N, int L>
 static int launch_one(const StepArgs<D, YD>& a, hipStream_t s)
 {
     const int64_t lanes = a.n_chains * L;
-    const unsigned grid = (unsigned)((lanes + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_for(lanes, BLOCK);
     if (a.tape_u) {
         if constexpr (L == 1)
             hipLaunchKernelGGL((sampler_kernel<ALGO, D, YD, N, 1, VAR_TAPE, GLABC_SCHED>), dim3(grid), dim3(BLOCK), 0, s, a);
@@ -38,7 +40,7 @@ static int launch_one(const StepArgs<D, YD>& a, hipStream_t s)
         hipLaunchKernelGGL((sampler_kernel<ALGO, D, YD, N, L, (YD == D ? VAR_GAUSS_UNIT : VAR_GENERIC), GLABC_SCHED>), dim3(grid), dim3(BLOCK), 0, s, a);
     else
         hipLaunchKernelGGL((sampler_kernel<ALGO, D, YD, N, L, VAR_GENERIC, GLABC_SCHED>), dim3(grid), dim3(BLOCK), 0, s, a);
-    return hipGetLastError() == hipSuccess ? GLABC_OK : GLABC_ERR_LAUNCH;
+    return launch_status();
 }
 
 template <int D, int YD, int N>
@@ -63,13 +65,7 @@ int launch_sampler_dim<GLABC_DIM, GLABC_YDIM, GLABC_SCHED>(int algo, int n_batch
 {
     constexpr int D = GLABC_DIM, YD = GLABC_YDIM;
     if (algo == ALGO_GLOBAL) return launch_one<ALGO_GLOBAL, D, YD, 1, 1>(a, s);
-    switch (n_batch) {
-#define GLABC_CASE(n) case n: return launch_lanes<D, YD, n>(lanes, a, s);
-        GLABC_CASE(1) GLABC_CASE(2) GLABC_CASE(3) GLABC_CASE(4) GLABC_CASE(5) GLABC_CASE(6) GLABC_CASE(7) GLABC_CASE(8)
-        GLABC_CASE(9) GLABC_CASE(10) GLABC_CASE(11) GLABC_CASE(12) GLABC_CASE(13) GLABC_CASE(14) GLABC_CASE(15) GLABC_CASE(16)
-#undef GLABC_CASE
-    default: return GLABC_ERR_ARG;
-    }
+    return dispatch_range<1, 16>(n_batch, GLABC_ERR_ARG, [&](auto n) { return launch_lanes<D, YD, decltype(n)::value>(lanes, a, s); });
 }
 
 }  // namespace glabc

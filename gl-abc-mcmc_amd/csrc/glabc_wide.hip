@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "glabc_dispatch.h"
+#include "glabc_launch.h"
 #include "glabc_lds_grant.h"
 #include "glabc_wide.h"
 
@@ -17,9 +19,9 @@ static int launch_wide_lg(const StepArgs<D, YD>& a, int N, hipStream_t s)
     const size_t lds = (size_t)wide_lds_bytes(L, N);
     static LdsGrant grant;                               // per instantiation, per device
     if (!grant_dynamic_lds(grant, (const void*)wide_kernel<D, YD, L, GM>, lds)) return GLABC_ERR_LAUNCH;
-    const unsigned grid = (unsigned)((a.n_chains + GROUPS - 1) / GROUPS);
+    const unsigned grid = grid_for(a.n_chains, GROUPS);
     hipLaunchKernelGGL((wide_kernel<D, YD, L, GM>), dim3(grid), dim3(WIDE_BLOCK), lds, s, a, N);
-    return hipGetLastError() == hipSuccess ? GLABC_OK : GLABC_ERR_LAUNCH;
+    return launch_status();
 }
 
 template <int D, int YD, int L>
@@ -36,13 +38,7 @@ static int launch_wide_l(const StepArgs<D, YD>& a, int N, hipStream_t s)
 template <int D, int YD>
 int launch_wide(const StepArgs<D, YD>& a, int N, int lanes, hipStream_t s)
 {
-    switch (lanes) {
-    case 8: return launch_wide_l<D, YD, 8>(a, N, s);
-    case 16: return launch_wide_l<D, YD, 16>(a, N, s);
-    case 32: return launch_wide_l<D, YD, 32>(a, N, s);
-    case 64: return launch_wide_l<D, YD, 64>(a, N, s);
-    default: return GLABC_ERR_ARG;
-    }
+    return dispatch_values<8, 16, 32, 64>(lanes, GLABC_ERR_ARG, [&](auto l) { return launch_wide_l<D, YD, decltype(l)::value>(a, N, s); });
 }
 
 template int launch_wide<1, 1>(const StepArgs<1, 1>&, int, int, hipStream_t);

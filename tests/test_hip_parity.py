@@ -1459,6 +1459,14 @@ def test_fast_math_decisions_follow_the_checker_on_the_kernels_own_draws(hip, or
           % (d, N, len(flipped), n, T))
 
 
+def test_fast_math_team_of_two_follows_the_checker(hip, oracle, monkeypatch):
+    """launches of the cases above are small, so they run as teams of three wavefronts (tests/test_launch_plan.py
+    test_fast_math); GLABC_TEAM_WAVES = 2 takes the same case through the other fast instantiation, team_sampler_kernel<..., NW = 2,
+    FAST>, which a default launch reaches only above 65 536 chains"""
+    monkeypatch.setenv("GLABC_TEAM_WAVES", "2")
+    test_fast_math_decisions_follow_the_checker_on_the_kernels_own_draws(hip, oracle, FAST_CASES[1])
+
+
 def test_fast_math_samples_the_same_law(hip):
     """65 536 chains x 1000 iterations of the bench configuration, exact and fast kernel: E theta^2 (analytic 2.081014), E|theta|
     and ESJD agree within 1e-3 relative plus four combined standard errors (north_star's tolerance for posterior moments / ESJD)"""

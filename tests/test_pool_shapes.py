@@ -421,10 +421,10 @@ class PoolCase:
     """Inputs of one (D, N) shape and what the checker makes of them -- host side only, so that the no-idle-run condition
     (some chain moved) can be looked at without a GPU."""
 
-    def __init__(self, oracle, d, N, n_iter=8):
+    def __init__(self, oracle, d, N, n_iter=8, shape=None):
         import oracle_lib
         self.d, self.N = d, N
-        self.step_size, self.n_chains = pool_shape(d, N)
+        self.step_size, self.n_chains = shape or pool_shape(d, N)
         self.model, self.local = abs_gauss_model(d)
         self.seed, self.gf, self.chain0 = 5 + d, 0.7, 7 + (1 << 33)
         self.n_iter = n_iter if self.n_chains > 1 else 24                 # one chain: enough iterations for it to move
@@ -506,8 +506,12 @@ def test_pool_entry_points_equal_checker_at_every_compiled_shape(hip, oracle, d,
     """glabc_pool_weights, glabc_kde_train_weights and glabc_glmcmc_nf_step for every compiled <D, N> against the checker, bit
     for bit: states, history row, kk (exhausted-pool guard included), n_moves and the moved-chain list (a set: the kernel's
     order is unspecified) with its count and reset counter."""
+    check_pool_case(hip, PoolCase(oracle, d, N))
+
+
+def check_pool_case(hip, case):
     from glabcmcmc_amd import engine
-    case = PoolCase(oracle, d, N)
+    d, N = case.d, case.N
     assert case.n_moves.sum() > 0                                          # two idle runs cannot pass
     rows, n = case.rows, case.n_chains
     tg, lg = dev(case.theta), dev(case.log_q)
@@ -553,6 +557,31 @@ def test_pool_entry_points_equal_checker_at_every_compiled_shape(hip, oracle, d,
         assert k == want["n_moved"] and int(nxt[0].item()) == 0
         assert np.array_equal(np.sort(listed[:k]), want["moved"])
         assert_untouched(listed[k:])
+
+
+# glabc_glmcmc_nf_step picks nf_step_kernel<D, N> out of N = 1 .. 16 at run time (launch_nf_step); the grid above reaches the
+# batch sizes of BATCHES.  The others, each at one D (every D twice) and at the smallest shape that can still go wrong: one
+# full wavefront plus one lane, three iterations, both step sizes
+OTHER_BATCHES = tuple(N for N in range(1, 17) if N not in BATCHES)
+
+
+def other_batch_case(oracle, N):
+    return PoolCase(oracle, 1 + OTHER_BATCHES.index(N) % 4, N, n_iter=3, shape=((1, 3)[N % 2], 65))
+
+
+def test_checker_pool_runs_at_the_other_batch_sizes_are_not_idle(oracle):
+    assert OTHER_BATCHES == (5, 6, 9, 10, 11, 12, 13, 14)
+    for N in OTHER_BATCHES:
+        case = other_batch_case(oracle, N)
+        assert (case.d, case.n_chains, case.n_iter) == (1 + OTHER_BATCHES.index(N) % 4, 65, 3)
+        assert case.n_moves.sum() > 0 and sum(s["n_moved"] for s in case.steps) == case.n_moves.sum(), N
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", OTHER_BATCHES)
+def test_nf_step_equals_checker_at_the_other_batch_sizes(hip, oracle, N):
+    """with the grid above, every N of 1 .. 16 runs against the checker, bit for bit, canaries on every output"""
+    check_pool_case(hip, other_batch_case(oracle, N))
 
 
 @pytest.mark.gpu
