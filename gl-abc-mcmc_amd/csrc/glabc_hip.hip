@@ -556,7 +556,8 @@ static int check_run(const glabc_model* m, const glabc_dist* local, const glabc_
     rc = check_dist(global, m->theta_dim, true);
     if (rc) return rc;
     const bool gamma = m->prior.kind == GLABC_DIST_GAMMA || global->kind == GLABC_DIST_GAMMA;
-    if (gamma && (m->sim_kind != GLABC_SIM_ABS_GAUSS || m->theta_dim > 4)) return GLABC_ERR_KIND;    // the instantiated Gamma variants
+    // the instantiated Gamma variants: |theta| + noise up to theta_dim 4, and g-and-k
+    if (gamma && m->sim_kind != GLABC_SIM_GK && (m->sim_kind != GLABC_SIM_ABS_GAUSS || m->theta_dim > 4)) return GLABC_ERR_KIND;
     if (gamma && r && r->tape) return GLABC_ERR_ARG;                // a tape has no Gamma variates
     if (!c || !r) return GLABC_ERR_NULL;
     if (int e = check_chains(c, isir ? CHAINS_ISIR : CHAINS_PLAIN)) return e;

@@ -15,6 +15,10 @@
 //
 // GLABC_RTC_WIDE (glabc_rtc_compile_wide) instantiates the lane-group GLMCMC kernel of glabc_wide.h instead, for every lanes-per-chain
 // value L = 8 / 16 / 32 / 64 the host may launch: the batch size is a launch argument there, so one program serves N = 17 .. 4096.
+//
+// GLABC_RTC_WITH_GAMMA (glabc_rtc_compile_ex / glabc_rtc_compile_wide_ex with the flag GLABC_RTC_GAMMA) adds the kernels of a Gamma prior /
+// importance / global proposal: sampler_kernel<.., VAR_GAMMA> at one lane per chain whatever GLABC_RTC_L is, its teams of three /
+// two wavefronts (GLABC_RTC_GAMMA_TEAM3 / _TEAM2, GLMCMC) and wide_kernel<.., true>.  Such a program holds no VAR_GAUSS_UNIT kernels.
 #pragma once
 
 #include "glabc_sampler.h"
@@ -29,19 +33,30 @@ template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 8, false>(const 
 template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 16, false>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
 template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 32, false>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
 template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 64, false>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+#ifdef GLABC_RTC_WITH_GAMMA
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 8, true>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 16, true>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 32, true>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 64, true>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+#endif
 #else
 template __global__ void sampler_kernel<GLABC_RTC_ALGO, GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_N, GLABC_RTC_L, VAR_GENERIC, 0>(
     const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>);
-#if GLABC_RTC_YD == GLABC_RTC_D && !defined(GLABC_USER_PRIOR) && !defined(GLABC_USER_DISCREPANCY) && !defined(GLABC_USER_KERNEL)
+#if GLABC_RTC_YD == GLABC_RTC_D && !defined(GLABC_USER_PRIOR) && !defined(GLABC_USER_DISCREPANCY) && !defined(GLABC_USER_KERNEL) && !defined(GLABC_RTC_WITH_GAMMA)
 // ... and the branch-free variant for unit-scale Gaussian prior / global proposal (chosen per launch by the host, as for the
 // built-in kernels: glabc_pack.h gauss_unit_config)
 template __global__ void sampler_kernel<GLABC_RTC_ALGO, GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_N, GLABC_RTC_L, VAR_GAUSS_UNIT, 0>(
     const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>);
 #endif
+#ifdef GLABC_RTC_WITH_GAMMA
+// ... and the Gamma variant (float64 draws and densities), one lane per chain: chain_step asserts !GM || L == 1
+template __global__ void sampler_kernel<GLABC_RTC_ALGO, GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_N, 1, VAR_GAMMA, 0>(
+    const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>);
+#endif
 
 // ... and the team geometry of glabc_team.h (two or three wavefronts per 64 chains: what the built-in GLMCMC kernels run at 16 384 ..
 // 131 072 chains), where the host found the configuration to fit (GLABC_RTC_TEAM3 / GLABC_RTC_TEAM2)
-#if GLABC_RTC_ALGO == 0 && (defined(GLABC_RTC_TEAM3) || defined(GLABC_RTC_TEAM2))
+#if GLABC_RTC_ALGO == 0 && (defined(GLABC_RTC_TEAM3) || defined(GLABC_RTC_TEAM2) || defined(GLABC_RTC_GAMMA_TEAM3) || defined(GLABC_RTC_GAMMA_TEAM2))
 }  // namespace glabc
 #include "glabc_team.h"
 namespace glabc {
@@ -54,7 +69,13 @@ GLABC_RTC_TEAM_INST(3, VAR_GENERIC)
 #ifdef GLABC_RTC_TEAM2
 GLABC_RTC_TEAM_INST(2, VAR_GENERIC)
 #endif
-#if GLABC_RTC_YD == GLABC_RTC_D && !defined(GLABC_USER_PRIOR) && !defined(GLABC_USER_DISCREPANCY) && !defined(GLABC_USER_KERNEL)
+#ifdef GLABC_RTC_GAMMA_TEAM3
+GLABC_RTC_TEAM_INST(3, VAR_GAMMA)
+#endif
+#ifdef GLABC_RTC_GAMMA_TEAM2
+GLABC_RTC_TEAM_INST(2, VAR_GAMMA)
+#endif
+#if GLABC_RTC_YD == GLABC_RTC_D && !defined(GLABC_USER_PRIOR) && !defined(GLABC_USER_DISCREPANCY) && !defined(GLABC_USER_KERNEL) && !defined(GLABC_RTC_WITH_GAMMA)
 #ifdef GLABC_RTC_TEAM3
 GLABC_RTC_TEAM_INST(3, VAR_GAUSS_UNIT)
 #endif
@@ -70,7 +91,7 @@ GLABC_RTC_TEAM_INST(2, VAR_GAUSS_UNIT)
 #include "glabc_team.h"
 namespace glabc {
 template __global__ void global_team_kernel<GLABC_RTC_D, GLABC_RTC_YD, VAR_GENERIC, 2>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, int);
-#if GLABC_RTC_YD == GLABC_RTC_D && !defined(GLABC_USER_PRIOR) && !defined(GLABC_USER_DISCREPANCY) && !defined(GLABC_USER_KERNEL)
+#if GLABC_RTC_YD == GLABC_RTC_D && !defined(GLABC_USER_PRIOR) && !defined(GLABC_USER_DISCREPANCY) && !defined(GLABC_USER_KERNEL) && !defined(GLABC_RTC_WITH_GAMMA)
 template __global__ void global_team_kernel<GLABC_RTC_D, GLABC_RTC_YD, VAR_GAUSS_UNIT, 2>(const StepArgs<GLABC_RTC_D, GLABC_RTC_YD>, int);
 #endif
 #endif

@@ -29,7 +29,7 @@ static int launch_one(const StepArgs<D, YD>& a, hipStream_t s)
             return GLABC_ERR_ARG;
     } else if (a.prior.kind == GLABC_DIST_GAMMA || a.global.kind == GLABC_DIST_GAMMA) {
 #if GLABC_SCHED == 0
-        if constexpr (L == 1 && D <= 4 && YD == D)
+        if constexpr (L == 1 && D <= 4)                             // |theta| + noise up to theta_dim 4, and g-and-k
             hipLaunchKernelGGL((sampler_kernel<ALGO, D, YD, N, 1, VAR_GAMMA, GLABC_SCHED>), dim3(grid), dim3(BLOCK), 0, s, a);
         else
             return GLABC_ERR_KIND;

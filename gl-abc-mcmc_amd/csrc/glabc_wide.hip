@@ -27,10 +27,8 @@ static int launch_wide_lg(const StepArgs<D, YD>& a, int N, hipStream_t s)
 template <int D, int YD, int L>
 static int launch_wide_l(const StepArgs<D, YD>& a, int N, hipStream_t s)
 {
-    if (a.prior.kind == GLABC_DIST_GAMMA || a.global.kind == GLABC_DIST_GAMMA) {      // Gamma importance proposal / prior
-        if constexpr (YD == D) return launch_wide_lg<D, YD, L, true>(a, N, s);
-        else return GLABC_ERR_KIND;
-    }
+    if (a.prior.kind == GLABC_DIST_GAMMA || a.global.kind == GLABC_DIST_GAMMA)        // Gamma importance proposal / prior
+        return launch_wide_lg<D, YD, L, true>(a, N, s);
     return launch_wide_lg<D, YD, L, false>(a, N, s);
 }
 

@@ -16,8 +16,11 @@ offset in a multi-GPU run), ``record_history`` (False: return None, keep only
 ``return_device`` (leave the result on the GPU), ``steps_per_launch``, ``verbose``.
 
 Dispatch (``path``): a Model and proposals that describe themselves (``descriptor()``; theta_dim 1..4 or the g-and-k
-shape; batch_size <= 4096) run in the fused kernels (above 16 proposals lane groups of a wavefront share a chain).  So does a
-``compiled.CompiledModel`` (a user's simulator compiled into those kernels at run time): up to 16 proposals in a register kernel
+shape; batch_size <= 4096) run in the fused kernels (above 16 proposals lane groups of a wavefront share a chain).  A
+``distribution.Gamma`` prior or importance proposal is fused on the |theta| + noise Model up to theta_dim 4, on g-and-k
+(``GK_set(prior=...)``) and on a ``CompiledModel`` (its programs are then compiled with the Gamma kernels); a Gamma local increment
+is a callback and runs split-phase.  A
+``compiled.CompiledModel`` (a user's simulator compiled into those kernels at run time) runs fused as well: up to 16 proposals in a register kernel
 compiled for the batch size, 17..4096 in the lane-group kernel compiled once per Model -- except that ``"auto"`` keeps one with a
 user prior on the split-phase path above 16 proposals (only that path redraws the 7 log(1e-10) prior sentinel), and falls back
 to it with a warning where that kernel fails to compile or fails its self-check.  ANY other Model object implementing the reference's callbacks
@@ -51,7 +54,7 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
             getattr(generic.try_descriptor(ABCset), "sim_kind", None) == _capi.SIM_USER:
         from .compiled import SimulatorCompileError, SimulatorSelfCheckError
         try:                                                       # a CompiledModel's lane-group program (compiled and checked once)
-            rtc = ABCset.program(_capi.ALGO_GLMCMC, batch_size)
+            rtc = generic.rtc_program(ABCset, generic.try_descriptor(ABCset), Importance_Proposal, _capi.ALGO_GLMCMC, batch_size)
         except (SimulatorCompileError, SimulatorSelfCheckError) as exc:
             warnings.warn("GLMCMC: the run-time compiled kernel for batch_size %d is unavailable, running the split-phase path "
                           "instead (%s)" % (int(batch_size), str(exc).splitlines()[0]), RuntimeWarning, stacklevel=2)
@@ -71,7 +74,7 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
     mirror = _host.HostMirror(hist) if _host.HostMirror.wanted(hist, single, return_device) else None   # rows leave for the host while the kernels run
     if model.sim_kind == _capi.SIM_USER:                           # compiled.CompiledModel: the simulator is run-time compiled C
         if rtc is None:                                            # (log_weight_old is computed at the first global move: `local` starts set)
-            rtc = ABCset.program(_capi.ALGO_GLMCMC, batch_size)
+            rtc = generic.rtc_program(ABCset, model, Importance_Proposal, _capi.ALGO_GLMCMC, batch_size)
     else:
         engine.init_weights(model, imp, chains)                    # GLMCMC.py:52-55
     engine.run_steps("glabc_glmcmc_steps", model, local, imp, chains, num_ite - 1, 1, engine.draw_seed(seed),

@@ -22,6 +22,7 @@ SIM_GK = 1
 SIM_USER = 2
 
 RTC_PRIOR_LOG_PROB, RTC_DISCREPANCY, RTC_LOG_KERNEL = 0, 1, 2      # glabc_rtc_model_rows `what`
+RTC_GAMMA = 1                  # glabc_rtc_compile_ex / glabc_rtc_compile_wide_ex `flags`
 VERSION = 301                  # include/glabc.h GLABC_VERSION
 STREAM_LAYOUT = 2              # include/glabc.h GLABC_STREAM_LAYOUT
 
@@ -269,6 +270,10 @@ ENTRY_POINTS = {
     "glabc_rtc_compile": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p,
                                     C.c_int64]),
     "glabc_rtc_compile_wide": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),
+    "glabc_rtc_compile_ex": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P(C.c_void_p),
+                                       C.c_char_p, C.c_int64]),
+    "glabc_rtc_compile_wide_ex": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P(C.c_void_p), C.c_char_p,
+                                            C.c_int64]),
     "glabc_rtc_steps": (C.c_int, [C.c_void_p, _P(Model), _P(Dist), _P(Dist), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_rtc_simulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_rtc_release": (None, [C.c_void_p]),

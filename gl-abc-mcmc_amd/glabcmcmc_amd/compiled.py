@@ -37,7 +37,13 @@ Model with a user prior on the split-phase path above 16 proposals (only that pa
 sentinel), and falls back to it with a warning where the wide program fails to compile or fails its check.  The object also
 implements the full duck-typed protocol (``generate_samples`` through the compiled simulator on rows, ``prior_log_prob`` /
 ``discrepancy`` / ``calculate_log_kernel`` through the row-wise kernels), so it works with every sampler, the split-phase
-path included.  Use + - * / fmaf sqrtf fabsf and the ``glabc_*`` functions of include/glabc_numerics.h (``glabc_expf``,
+path included.
+
+A ``distribution.Gamma`` as the Model's prior and / or as the importance / global proposal runs fused too: the samplers then ask for
+a program compiled with ``GLABC_RTC_GAMMA`` (``program(..., gamma=True)``, a program of its own in the cache), which holds the
+Gamma kernels next to the generic ones, and its self-check runs them -- with the caller's proposal, positive start states.
+
+Use + - * / fmaf sqrtf fabsf and the ``glabc_*`` functions of include/glabc_numerics.h (``glabc_expf``,
 ``glabc_logf``, ``glabc_sincos2pi`` ...) for results that a CPU build of the same source reproduces bit for bit.
 """
 import ctypes as C
@@ -81,21 +87,36 @@ class CompiledModel:
     # ---- run-time compiled programs: one per (algorithm, batch size) up to 16, one wide program for GLMCMC above ---------
     WIDE = "wide"
 
-    def program(self, algo, batch_size=1):
+    GAMMA = "gamma"
+
+    def program(self, algo, batch_size=1, gamma=False, proposal=None):
+        """gamma: the program with the Gamma kernels (GLABC_RTC_GAMMA) -- what a sampler asks for when the prior or its importance /
+        global proposal (`proposal`: the object, for the self-check) is a Gamma.  A Model whose prior is a Gamma has no other."""
         algo = int(algo)
         n = 1 if algo == _capi.ALGO_GLOBALMCMC else int(batch_size)
         wide = algo == _capi.ALGO_GLMCMC and n > _capi.MAX_BATCH
         if wide and n > _capi.MAX_BATCH_WIDE:
             raise ValueError("batch_size %d: the fused kernels take 1..%d" % (n, _capi.MAX_BATCH_WIDE))
+        gamma = bool(gamma) or self._gamma_prior()
         key = (algo, self.WIDE) if wide else (algo, n)   # the program
         check = (algo, n)                                # its self-check: once per batch size (the wide one serves many)
+        if gamma:
+            key, check = key + (self.GAMMA,), check + (self.GAMMA,)
         if key in self._failed:
             raise SimulatorSelfCheckError(self._failed[key])
         if key not in self._programs:
             handle = C.c_void_p()
             log = C.create_string_buffer(1 << 16)
             src = self.simulator_source.encode()
-            if wide:
+            if gamma and wide:
+                name = "glabc_rtc_compile_wide_ex"
+                rc = _capi.lib().glabc_rtc_compile_wide_ex(src, self.theta_dim, self.y_dim, self.noise_dim, _capi.RTC_GAMMA,
+                                                           C.byref(handle), log, len(log))
+            elif gamma:
+                name = "glabc_rtc_compile_ex"
+                rc = _capi.lib().glabc_rtc_compile_ex(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, _capi.RTC_GAMMA,
+                                                      C.byref(handle), log, len(log))
+            elif wide:
                 name = "glabc_rtc_compile_wide"
                 rc = _capi.lib().glabc_rtc_compile_wide(src, self.theta_dim, self.y_dim, self.noise_dim, C.byref(handle), log, len(log))
             else:
@@ -108,14 +129,17 @@ class CompiledModel:
         if check not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
             self._checked.add(check)                     # before the check: self_check re-enters program() through the samplers
             try:
-                self.self_check(algo, n)
+                if gamma:
+                    self.self_check(algo, n, gamma=True, proposal=proposal)
+                else:
+                    self.self_check(algo, n)
             except BaseException as exc:
                 # a program that failed (or did not finish) its check must never be handed out: release it, and keep the
                 # verdict so that every later call raises again instead of sampling with a miscompiled kernel.  The wide program
                 # is one code object for all batch sizes above 16: the checks it passed at other batch sizes go with it
                 self._checked.discard(check)
                 if wide:
-                    self._checked -= {k for k in self._checked if k[0] == algo and k[1] > _capi.MAX_BATCH}
+                    self._checked -= {k for k in self._checked if k[0] == algo and k[1] > _capi.MAX_BATCH and len(k) == len(check)}
                 handle = self._programs.pop(key, None)
                 if handle is not None:
                     _capi.lib().glabc_rtc_release(handle)
@@ -124,13 +148,22 @@ class CompiledModel:
                 raise
         return self._programs[key]
 
-    def self_check(self, algo, batch_size=1, n_chains=512, steps=4, seed=20240229):
+    def _gamma_prior(self):
+        try:
+            return self.prior.descriptor().kind == _capi.DIST_GAMMA
+        except (AttributeError, NotImplementedError, ValueError):
+            return False
+
+    def self_check(self, algo, batch_size=1, n_chains=512, steps=4, seed=20240229, gamma=False, proposal=None):
         """The freshly compiled kernel against the split-phase path on the same Philox streams: a few iterations of
         `n_chains` synthetic chains through both (same simulator binary for the rows, library kernels for everything
         else -- the path tests/test_generic_path.py holds to the CPU checker), compared bit for bit.  Runs once per program
         (a few ms; the wide program once per batch size, at the lanes per chain the library launches for it);
         GLABC_RTC_SELF_CHECK=0 skips it.  It exists because the run-time compiler has miscompiled this very
-        kernel before: a mismatch raises instead of returning samples from the wrong law."""
+        kernel before: a mismatch raises instead of returning samples from the wrong law.
+        gamma: the check of a GLABC_RTC_GAMMA program runs its Gamma kernel -- the importance / global proposal is `proposal` (the
+        sampler call's), else the prior when that is a Gamma, else Gamma(shape 4, rate 2) per coordinate; the chains start at
+        positive states around a Gamma's mean."""
         from .GlobalMCMC import GlobalMCMC
         from .GLMCMC import GLMCMC
         dev = engine.require_device(None)
@@ -139,7 +172,21 @@ class CompiledModel:
         pd = self.prior.descriptor()
         loc = torch.tensor([pd.p0[j] for j in range(d)])
         scale = torch.tensor([pd.p2[j] for j in range(d)])
-        if pd.kind == _capi.DIST_UNIFORM:                             # p0 = low, p2 = high - low
+        if gamma or pd.kind == _capi.DIST_GAMMA:
+            if proposal is not None:
+                imp = proposal
+            elif pd.kind == _capi.DIST_GAMMA:
+                imp = self.prior
+            else:
+                imp = distribution.Gamma(torch.full((d,), 4.0), torch.full((d,), 2.0))
+            gd = pd if pd.kind == _capi.DIST_GAMMA else imp.descriptor()
+            if gd.kind != _capi.DIST_GAMMA:
+                raise ValueError("a Gamma program is checked with a Gamma prior or proposal")
+            shape = torch.tensor([gd.p0[j] for j in range(d)])        # p0 = shape, p2 = 1 / rate
+            mean = shape * torch.tensor([gd.p2[j] for j in range(d)])
+            theta0 = mean * torch.exp(0.3 * torch.randn(n_chains, d, generator=g))
+            spread = mean / torch.sqrt(shape)                         # the Gamma's standard deviation
+        elif pd.kind == _capi.DIST_UNIFORM:                           # p0 = low, p2 = high - low
             theta0 = loc + scale * torch.rand(n_chains, d, generator=g)
             imp = distribution.Uniform(d, loc, loc + scale)
             spread = scale / 4.0

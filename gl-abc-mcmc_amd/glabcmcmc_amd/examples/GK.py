@@ -3,7 +3,8 @@
 The reference tree contains no such model (its only Model is examples/Mixture.py), so this one is the build's own,
 written against the reference's duck-typed Model protocol (examples/Mixture.py:5-53):
 
-    theta = (A, B, g, k),  prior Uniform(0, 10)^4
+    theta = (A, B, g, k),  prior Uniform(0, 10)^4, or ``GK_set(epsilon, prior=...)``: any distribution.* object with a descriptor --
+        e.g. distribution.Gamma for the positive parameters, which the fused kernels evaluate in double (GLABC_DIST_GAMMA)
     one simulation = the ORDER STATISTICS of y_dim = 8 draws of the g-and-k distribution,
         y_j = A + B (1 + c tanh(g z_j / 2)) (1 + z_j^2)^k z_j,   z_j ~ N(0, 1),   c = 0.8
     y_obs = that quantile function for (A, B, g, k) = (3, 1, 2, 0.5) at the normal scores of (j - 0.5)/8
@@ -29,9 +30,10 @@ def gk_quantile(z, A, B, g, k, c=0.8):
 
 
 class GK_set:
-    def __init__(self, epsilon, c=0.8):
+    def __init__(self, epsilon, c=0.8, prior=None):
         self.epsilon = epsilon
         self.c = c
+        self._prior_override = prior                # another prior than Uniform(0, 10)^4, as Mixture_set(prior=...)
         self.theta_dim = 4
         self.y_dim = Y_DIM
         p = (torch.arange(1, Y_DIM + 1, dtype=torch.float64) - 0.5) / Y_DIM
@@ -39,6 +41,8 @@ class GK_set:
         self.y_obs = gk_quantile(z, *TRUE_THETA, c=c).view(1, -1)
 
     def _prior(self):
+        if self._prior_override is not None:
+            return self._prior_override
         return distribution.Uniform(4, torch.zeros(4), torch.full((4,), 10.0))
 
     def _kernel(self, epsilon):

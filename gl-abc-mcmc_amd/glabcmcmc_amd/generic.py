@@ -14,7 +14,9 @@ one iteration for ALL chains is
 
 so the decisions are taken by the same arithmetic as in the fused kernels, and the Model is called
 ``batch_size * n_chains`` rows at a time instead of ``batch_size`` rows.  Proposal objects without a ``glabc_dist``
-descriptor (``Gamma``, ``GaussianMixture``, a user's class) are callbacks too: ``forward`` / ``sample`` / ``log_prob``.
+descriptor (``GaussianMixture``, a user's class; a ``Gamma`` as the local increment) are callbacks too: ``forward`` / ``sample`` /
+``log_prob``.  A ``Gamma`` prior or importance / global proposal is no reason to come here: the fused kernels take it on the
+|theta| + noise Model up to theta_dim 4, on g-and-k and on a ``CompiledModel`` (``fused_supported``).
 
 Optional extension of the protocol: a Model with ``noise_dim`` and ``simulate_from_noise(theta, eps)`` receives the
 simulator's standard normals from the run's Philox stream (reproducible from ``seed``, independent of sharding); without
@@ -55,10 +57,20 @@ def dist_descriptor(obj, dim, gamma=False):
     return d
 
 
+def rtc_program(ABCset, model_desc, proposal, algo, batch_size=1):
+    """a CompiledModel's program for a sampler call: the one with the Gamma kernels (GLABC_RTC_GAMMA) when the Model's prior or the
+    importance / global proposal is a Gamma, checked with the caller's proposal"""
+    d = try_descriptor(proposal)
+    if model_desc.prior.kind == _capi.DIST_GAMMA or (isinstance(d, _capi.Dist) and d.kind == _capi.DIST_GAMMA):
+        return ABCset.program(algo, batch_size, gamma=True, proposal=proposal)
+    return ABCset.program(algo, batch_size)
+
+
 def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, gamma_ok=False):
     """Can the fused kernels (glabc_glmcmc_steps / glabc_globalmcmc_steps / glabc_glmala_steps) run this configuration?
     gamma_ok: the entry point knows GLABC_DIST_GAMMA as the LAST proposal (importance / global) and as the Model's prior --
-    GLMCMC and GlobalMCMC on the |theta| + noise Model up to theta_dim 4 (include/glabc.h)."""
+    GLMCMC and GlobalMCMC on the |theta| + noise Model up to theta_dim 4, on g-and-k and on a compiled.CompiledModel, whose
+    programs are then compiled with GLABC_RTC_GAMMA (include/glabc.h)."""
     m = try_descriptor(ABCset)
     if m is None or not isinstance(m, _capi.Model):
         return False
@@ -71,7 +83,8 @@ def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, ga
             if i != len(proposals) - 1:
                 return False                                 # a Gamma local increment: callback
             gamma = True
-    if gamma and not (gamma_ok and m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4):
+    if gamma and not (gamma_ok and ((m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4) or m.sim_kind == _capi.SIM_GK or
+                                    (m.sim_kind == _capi.SIM_USER and hasattr(ABCset, "program")))):
         return False
     if m.sim_kind == _capi.SIM_USER:
         # compiled.CompiledModel: register kernels compiled per batch size up to GLABC_MAX_BATCH; above, where the caller's entry

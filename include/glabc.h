@@ -91,7 +91,11 @@ typedef struct glabc_dist {
  *             (include/glabc_numerics.h: Marsaglia-Tsang on the chain's Philox stream), theta'_q = (float) z_q,
  *             log q' = (float) sum_q log(pdf(z_q))  -- the density of the double variate, summed in torch.sum's float64 order
  *   log_prob: (float) sum_q log(pdf((double) theta_q)), -inf outside the support or where the pdf underflows (distribution.py:136)
- * which is what the split-phase path does with a Gamma object's callbacks (results rounded to float32 for glabc_select). */
+ * which is what the split-phase path does with a Gamma object's callbacks (results rounded to float32 for glabc_select).
+ * Where the fused samplers take it: glabc_glmcmc_steps (every batch size) and glabc_globalmcmc_steps on GLABC_SIM_ABS_GAUSS with
+ * theta_dim <= 4 and on GLABC_SIM_GK; glabc_rtc_steps on a program compiled with GLABC_RTC_GAMMA (glabc_rtc_compile_ex /
+ * glabc_rtc_compile_wide_ex).  Still refused: theta_dim 5..8 (GLABC_ERR_KIND), a tape and GLABC_MATH_FAST (GLABC_ERR_ARG),
+ * glabc_glmala_steps and the pool entry points (GLABC_ERR_KIND), a program compiled without the flag (GLABC_ERR_ARG). */
 
 /* ---- the Model callbacks: glabcmcmc/examples/Mixture.py:5-53 ------------- */
 typedef enum glabc_sim_kind {
@@ -186,7 +190,8 @@ typedef struct glabc_run {
                                       (DESIGN.md 4.0), or 1 / 2 / 4 lanes cooperating on one chain's batch_size proposals (8 / 16 /
                                       32 / 64 when batch_size > GLABC_MAX_BATCH).  A non-zero value also keeps a launch off the team
                                       kernels unless GLABC_DEBUG_TEAM asks for them; it is capped by what batch_size can feed (4
-                                      lanes need 3 proposals) and is one lane for GlobalMCMC, a tape and the Gamma variant */
+                                      lanes need 3 proposals) and is one lane for GlobalMCMC, a tape and the Gamma variant (every Model that
+                                      takes a Gamma: |theta| + noise, g-and-k, a run-time compiled program's Gamma entry) */
     int32_t debug_flags;           /* 0, or GLABC_DEBUG_* bits: execution strategy only, never changes results */
     const uint32_t* step0_device;  /* glabc_propose / glabc_propose_redraw / glabc_select only: NULL, or a DEVICE word holding the
                                       iteration index of this call.  The kernels then read the index from it (Philox counter
@@ -236,7 +241,9 @@ typedef struct glabc_draws_out {   /* device arrays covering exactly the call's 
 #define GLABC_DEBUG_TEAM 4
 /* (Round 3: teams of two / three wavefronts also run the Gamma variant, the g-and-k Model, GlobalMCMC -- glabc_globalmcmc_steps: a
  * helper wavefront draws an iteration's random numbers a chunk of iterations ahead -- and the run-time compiled kernels of
- * glabc_rtc_steps; the same two bits force / forbid the geometry there.) */
+ * glabc_rtc_steps; the same two bits force / forbid the geometry there.  The Gamma variant has teams on g-and-k -- three
+ * wavefronts for batch_size 3..7, two for 2..9, one lane per chain above -- and in a GLABC_RTC_GAMMA program; GlobalMCMC with a
+ * Gamma always runs one lane per chain.) */
 /* One lane per chain, theta_dim 1..4 (not g-and-k), launches of at most two wavefronts per SIMD: the library picks the build of the kernels scheduled for
  * instruction-level parallelism; this bit picks the default-schedule build (the one larger launches get) -- so that a test
  * can walk EVERY instantiation with small launches (tests/test_slp_twin.py). */
@@ -475,6 +482,20 @@ int glabc_rtc_compile(const char* simulator_source, int32_t algo, int32_t theta_
  * gives a workgroup.  glabc_rtc_simulate / glabc_rtc_hooks / glabc_rtc_model_rows accept such a program unchanged. */
 int glabc_rtc_compile_wide(const char* simulator_source, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
                            glabc_rtc_program** out, char* log, int64_t log_size);
+/* The two entry points above with `flags`: 0 builds exactly what they build; any bit but GLABC_RTC_GAMMA is GLABC_ERR_ARG.
+ * GLABC_RTC_GAMMA: the program also holds the kernels of a GLABC_DIST_GAMMA prior and / or importance / global proposal, and
+ * glabc_rtc_steps accepts such descriptors on it (on any other program they are GLABC_ERR_ARG; `local` is never a Gamma).
+ *   register program  the generic kernels as without the flag, less the unit-Gaussian variants (speed only), plus the Gamma entry at
+ *                     one lane per chain (whatever lane count the generic entry was given) and, for GLMCMC, its teams of two and
+ *                     three wavefronts where the batch's candidates fit the LDS budget; GlobalMCMC with a Gamma runs the one-lane entry
+ *   wide program      wide_kernel with and without the Gamma at 8 / 16 / 32 / 64 lanes; spill notes of both go to `log`
+ * A launch whose prior and global proposal are no Gamma runs the generic kernels of the same program.  With a user prior hook
+ * (GLABC_USER_PRIOR) the hook stays the prior and only the proposal is the Gamma. */
+#define GLABC_RTC_GAMMA 1u
+int glabc_rtc_compile_ex(const char* simulator_source, int32_t algo, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
+                         int32_t batch_size, uint32_t flags, glabc_rtc_program** out, char* log, int64_t log_size);
+int glabc_rtc_compile_wide_ex(const char* simulator_source, int32_t theta_dim, int32_t y_dim, int32_t noise_dim, uint32_t flags,
+                              glabc_rtc_program** out, char* log, int64_t log_size);
 int glabc_rtc_steps(const glabc_rtc_program* program, const glabc_model* model, const glabc_dist* local, const glabc_dist* global,
                     const glabc_chains* chains, const glabc_run* run, void* stream);
 /* generate_samples(theta, 1) of the compiled simulator on n row-major points: theta[n][theta_dim], eps[n][noise_dim] -> y[n][y_dim] */
