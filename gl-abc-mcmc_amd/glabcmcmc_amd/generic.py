@@ -18,11 +18,18 @@ descriptor (``GaussianMixture``, a user's class; a ``Gamma`` as the local increm
 ``log_prob``.  A ``Gamma`` prior or importance / global proposal is no reason to come here: the fused kernels take it on the
 |theta| + noise Model up to theta_dim 4, on g-and-k and on a ``CompiledModel`` (``fused_supported``).
 
+``SplitPhase`` owns what every loop here needs -- chains, Philox key, ``ModelCallbacks``, the buffers and the C structs of the
+two kernels -- and launches them (``at`` / ``propose`` / ``select`` / ``finish``).  ``run`` (GLMCMC, GlobalMCMC) drives an
+``Iteration`` on it, eagerly or as a replayed hipGraph whose segments, roll-backs and recaptures ``replay_segments`` decides
+without touching torch; ``PoolSampler`` (GLMCMC_NF, AGLMCMC) is a ``SplitPhase`` with per-chain proposal pools; ``run_glmala``
+adds the MALA move in torch.
+
 Optional extension of the protocol: a Model with ``noise_dim`` and ``simulate_from_noise(theta, eps)`` receives the
 simulator's standard normals from the run's Philox stream (reproducible from ``seed``, independent of sharding); without
 it ``generate_samples(theta, 1)`` draws from whatever generator the Model uses.
 """
 import ctypes as C
+import itertools
 import math
 
 import numpy as np
@@ -116,13 +123,14 @@ class ModelCallbacks:
         self.where = None if self.auto else callback_device
         self.noise_dim = int(getattr(abc_set, "noise_dim", 0)) if hasattr(abc_set, "simulate_from_noise") else 0
 
-    def _back(self, t, rows):
-        t = torch.as_tensor(t)
-        return t.detach().to(device=self.device, dtype=torch.float32).reshape(rows, -1).contiguous()
-
-    def _call(self, fn):
-        """fn(on_cuda: bool)"""
-        return fn(self.where != "cpu")
+    def _eval(self, name, *args):
+        """Model.<name>(*args) as a float32 (rows, -1) tensor on the device; the Model is handed CPU copies of the tensors among
+        `args` when its code cannot work with CUDA tensors (where == 'cpu')"""
+        rows = args[0].shape[0]
+        if self.where == "cpu":
+            args = [a.cpu() if torch.is_tensor(a) else a for a in args]
+        out = torch.as_tensor(getattr(self.m, name)(*args))
+        return out.detach().to(device=self.device, dtype=torch.float32).reshape(rows, -1).contiguous()
 
     def probe(self, theta_rows, y_rows):
         """'auto': decide once, before the loop, where the callbacks run.  A Model written against CPU tensors (the
@@ -141,19 +149,24 @@ class ModelCallbacks:
             self.where = "cpu"
 
     def prior(self, theta):
-        rows = theta.shape[0]
-        return self._call(lambda cuda: self._back(self.m.prior_log_prob(theta if cuda else theta.cpu()), rows)).view(-1)
+        return self._eval("prior_log_prob", theta).view(-1)
 
     def kernel(self, y):
-        rows = y.shape[0]
-        return self._call(lambda cuda: self._back(self.m.calculate_log_kernel(y if cuda else y.cpu()), rows)).view(-1)
+        return self._eval("calculate_log_kernel", y).view(-1)
 
     def simulate(self, theta, noise):
-        rows = theta.shape[0]
         if self.noise_dim:
-            return self._call(lambda cuda: self._back(
-                self.m.simulate_from_noise(theta if cuda else theta.cpu(), noise if cuda else noise.cpu()), rows))
-        return self._call(lambda cuda: self._back(self.m.generate_samples(theta if cuda else theta.cpu(), 1), rows))
+            return self._eval("simulate_from_noise", theta, noise)
+        return self._eval("generate_samples", theta, 1)
+
+    def discrepancy(self, y):
+        return self._eval("discrepancy", y).view(-1)
+
+    def kernel_of_discrepancy(self, dis, x, eps):
+        """calculate_log_kernel_dis(dis, eps) (AGLMCMC.py:199) if the Model has it, else calculate_log_kernel(x, eps)"""
+        if hasattr(self.m, "calculate_log_kernel_dis"):
+            return self._eval("calculate_log_kernel_dis", dis, eps).view(-1)
+        return self._eval("calculate_log_kernel", x, eps).view(-1)
 
 
 class ProposalCallbacks:
@@ -186,6 +199,237 @@ class ProposalCallbacks:
         return self._dev(out, theta.shape[0]).view(-1)
 
 
+def _ref(desc):
+    return C.byref(desc) if desc is not None else None
+
+
+class SplitPhase:
+    """The working set of a split-phase loop, whichever sampler runs it: the chains, the Philox key, the Model's callbacks, the
+    candidate and draw buffers glabc_propose fills, the current state's prior / kernel values that glabc_select carries, the
+    history, and the three C structs (glabc_step_io, glabc_chains, glabc_run) that point at all of them."""
+
+    def __init__(self, ABCset, num_ite, Initial_theta, Initial_y, device, chain0, seed, batch_size, global_frequency,
+                 callback_device, record_history, stats):
+        self.lib = _capi.lib()
+        self.dev, self.chains, self.single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
+        dev, chains = self.dev, self.chains
+        self.n, self.d, self.yd = chains.n, chains.d, chains.yd
+        self.N, self.num_ite, self.stats = int(batch_size), num_ite, stats
+        n, d, N = self.n, self.d, self.N
+        self.key = engine.draw_seed(seed)
+        self.model = ModelCallbacks(ABCset, dev, callback_device)
+        self.nd = nd = self.model.noise_dim
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.theta_prop = torch.zeros(N * n, d, **f32)
+        self.log_q = torch.zeros(N * n, **f32)
+        self.sim_noise = torch.zeros(N * n, nd, **f32) if nd else None
+        self.log_u = torch.zeros(n, **f32)
+        self.u_res = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.is_global = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.model.probe(chains.theta.t(), chains.y.t())
+        # callbacks of the initial state (GLMCMC.py:52-55): carried from here on by glabc_select
+        self.prior_cur = self.model.prior(chains.theta.t().contiguous()).clone()
+        self.kern_cur = self.model.kernel(chains.y.t().contiguous()).clone()
+        self.hist = _host.allocate_history(num_ite, chains, record_history)
+        self._hist_ptr, self._hist_row_bytes = (self.hist.data_ptr(), self.hist[0].numel() * 4) if self.hist is not None else (0, 0)
+
+        io = self.io = _capi.StepIO()
+        io.n_prop, io.theta_dim, io.y_dim, io.noise_dim = N, d, self.yd, nd
+        io.theta_prop, io.log_q = self.theta_prop.data_ptr(), self.log_q.data_ptr()
+        io.sim_noise = self.sim_noise.data_ptr() if nd else None
+        io.log_u, io.u_res, io.is_global = self.log_u.data_ptr(), self.u_res.data_ptr(), self.is_global.data_ptr()
+        io.prior_cur, io.kern_cur = self.prior_cur.data_ptr(), self.kern_cur.data_ptr()
+        self.cs = chains.struct()
+        run_ = self.run_ = _capi.Run()
+        run_.seed, run_.n_steps, run_.global_frequency, run_.batch_size, run_.hist_stride = self.key, 1, float(global_frequency), N, n
+        if stats is not None:
+            self._moments = stats.struct()
+            run_.moments = C.pointer(self._moments)
+        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)      # of the construction; a capture passes its own
+        self.held = ()                                                             # tensors whose addresses the StepIO holds
+
+    def at(self, i):
+        """the next launches are iteration i: its Philox index and its row of the history"""
+        self.run_.step0 = i
+        self.run_.history = self._hist_ptr + i * self._hist_row_bytes if self.hist is not None else None
+
+    def propose(self, algo, local_desc, global_desc, stream=None):
+        """glabc_propose: every random draw of the iteration, and the candidates of the proposals that have a descriptor"""
+        _capi.check(self.lib.glabc_propose(algo, _ref(local_desc), _ref(global_desc), C.byref(self.cs), C.byref(self.run_),
+                                           C.byref(self.io), self.stream if stream is None else stream), "glabc_propose")
+
+    def select(self, algo, global_desc, prior_prop, y_prop, kern_prop, q_cur=None, stream=None):
+        """glabc_select on the candidates' callback values (q_cur: a callback proposal's log-density of the current states)"""
+        self.held = (prior_prop, y_prop, kern_prop, q_cur)
+        io = self.io
+        io.prior_prop, io.y_prop, io.kern_prop = prior_prop.data_ptr(), y_prop.data_ptr(), kern_prop.data_ptr()
+        if q_cur is not None:
+            io.q_cur = q_cur.data_ptr()
+        _capi.check(self.lib.glabc_select(algo, _ref(global_desc), C.byref(self.cs), C.byref(self.run_), C.byref(io),
+                                          self.stream if stream is None else stream), "glabc_select")
+
+    def finish(self, filelocation, csv_variant, verbose, return_device):
+        if self.stats is not None:
+            self.stats.steps += self.num_ite - 1
+        return _host.finish(self.hist, self.chains, self.single, filelocation, csv_variant, verbose and self.single, return_device)
+
+
+class Iteration:
+    """One iteration of GLMCMC or GlobalMCMC for all chains of a SplitPhase: glabc_propose, the callback proposals, the Model's
+    prior with the sentinel redraw of GLMCMC.py:92-93, simulate / kernel, glabc_select."""
+
+    def __init__(self, sp, algo, Local_Proposal, Global_Proposal, sentinel_redraw, max_redraws):
+        self.sp, self.algo, self.max_redraws = sp, algo, max_redraws
+        self.local_desc = dist_descriptor(Local_Proposal, sp.d) if Local_Proposal is not None else None
+        self.global_desc = dist_descriptor(Global_Proposal, sp.d, gamma=True)
+        self.local_cb = ProposalCallbacks(Local_Proposal, sp.dev) if (self.local_desc is None and Local_Proposal is not None) else None
+        self.global_cb = ProposalCallbacks(Global_Proposal, sp.dev) if self.global_desc is None else None
+        self.redraw = sentinel_redraw and algo == _capi.ALGO_GLMCMC
+        self.n_redrawn = torch.zeros(1, dtype=torch.int32, device=sp.dev)
+        self.col_index = torch.arange(sp.n, device=sp.dev).view(1, sp.n)
+        self.n_valid = torch.full((sp.n,), sp.N, dtype=torch.int32, device=sp.dev)
+        if self.global_cb is not None and algo == _capi.ALGO_GLMCMC:
+            sp.io.n_valid = self.n_valid.data_ptr()
+
+    def __call__(self, i, rounds=0, violations=None):
+        """on torch's current stream.  i = None: the index is read from glabc_run.step0_device (a captured iteration).
+        violations: a device counter -- the sentinel check takes its captured form, `rounds` redraw rounds and a count of the
+        candidates they left at the sentinel; None: the eager loop, which asks the device after every round."""
+        sp = self.sp
+        stream = C.c_void_p(torch.cuda.current_stream(sp.dev).cuda_stream)
+        if i is not None:
+            sp.at(i)
+        sp.propose(self.algo, self.local_desc, self.global_desc, stream)
+        if self.global_cb is not None or self.local_cb is not None:
+            self.callback_proposals()
+        prior_prop = sp.model.prior(sp.theta_prop)                     # GLMCMC.py:74,92,96
+        sp.io.prior_prop = prior_prop.data_ptr()
+        if self.redraw and violations is not None:
+            self.redraw_captured(prior_prop, rounds, violations, stream)
+        elif self.redraw:
+            self.redraw_eager(prior_prop, stream)
+        y_prop = sp.model.simulate(sp.theta_prop, sp.sim_noise)        # GLMCMC.py:71,94
+        if y_prop.shape[1] != sp.yd:
+            raise ValueError("generate_samples returned %d columns, Initial_y has %d" % (y_prop.shape[1], sp.yd))
+        kern_prop = sp.model.kernel(y_prop)                            # GLMCMC.py:72,96
+        # Importance_Proposal.log_prob(Theta_old), GLMCMC.py:63
+        q_cur = self.global_cb.log_prob(sp.chains.theta.t().contiguous()) if self.global_cb is not None else None
+        sp.select(self.algo, self.global_desc, prior_prop, y_prop, kern_prop, q_cur, stream)
+
+    def callback_proposals(self):
+        """candidates of the proposals that are callbacks, over what glabc_propose wrote for the ones that are not"""
+        sp, n, N = self.sp, self.sp.n, self.sp.N
+        theta_prop, log_q = sp.theta_prop, sp.log_q
+        glob_rows = (sp.is_global != 0)
+        if self.global_cb is not None:                                 # Importance_Proposal.forward(batch_size), GLMCMC.py:66
+            z, lq = self.global_cb.forward(N * n)
+            if self.local_cb is None:                                  # keep the kernel's local-move rows
+                keep_rows = torch.zeros(N * n, dtype=torch.bool, device=sp.dev)
+                keep_rows[:n] = ~glob_rows
+                z = torch.where(keep_rows.view(-1, 1), theta_prop, z)
+            theta_prop.copy_(z)
+            log_q.copy_(lq)
+            if self.algo == _capi.ALGO_GLMCMC:
+                # GLMCMC.py:67-70: proposals with a NaN coordinate are dropped BEFORE the Model sees them; the weight vector
+                # is then shorter.  Only a callback proposal can produce them.  Stays on the device: the chain's valid rows
+                # move to the front in their order (the k-th survivor is simulated with the k-th noise row, as the
+                # reference's generate_samples(Theta_prop0) draws for the shortened batch), glabc_select gets the count.
+                bad = torch.isnan(theta_prop).any(1).view(N, n) & glob_rows.view(1, n)
+                order = torch.argsort(bad.to(torch.uint8), dim=0, stable=True)
+                rows = (order * n + self.col_index).view(-1)
+                theta_prop.copy_(theta_prop[rows])
+                log_q.copy_(log_q[rows])
+                self.n_valid.copy_((N - bad.sum(0)).to(torch.int32))
+        if self.local_cb is not None:                                  # Local_Proposal.sample(1) + Theta_old, GLMCMC.py:91
+            row0_local = self.local_cb.sample(n) + sp.chains.theta.t()
+            theta_prop[:n] = torch.where(glob_rows.view(-1, 1), theta_prop[:n], row0_local)
+
+    def _redraw_kernel(self, rnd, counter, stream):
+        sp = self.sp
+        _capi.check(sp.lib.glabc_propose_redraw(_ref(self.local_desc), C.byref(sp.cs), C.byref(sp.run_), C.byref(sp.io), rnd,
+                                                counter.data_ptr(), stream), "glabc_propose_redraw")
+
+    def redraw_captured(self, prior_prop, rounds, violations, stream):
+        """The reference's loop (GLMCMC.py:92-93) ends on a host read, which a hipGraph cannot hold, so a capture holds a BOUNDED
+        number of its rounds -- redraw the local candidates whose prior is the sentinel (a round without one is a no-op: the
+        kernel touches nothing and the prior of an unchanged row is the same number), evaluate the prior again -- and one more
+        launch of the redraw kernel that only COUNTS the candidates still at the sentinel after them, into `violations`, which
+        is never zeroed here: replay_segments reads it once per segment."""
+        n = self.sp.n
+        for rnd in range(1, rounds + 1):
+            self._redraw_kernel(rnd, self.n_redrawn, stream)
+            prior_prop[:n] = self.sp.model.prior(self.sp.theta_prop[:n])
+        self._redraw_kernel(rounds + 1, violations, stream)
+
+    def redraw_eager(self, prior_prop, stream):
+        """GLMCMC.py:92-93 as written: redraw until no local candidate's prior is the sentinel"""
+        sp, n = self.sp, self.sp.n
+        for rnd in range(1, self.max_redraws + 1):
+            if self.local_cb is None:
+                self.n_redrawn.zero_()
+                self._redraw_kernel(rnd, self.n_redrawn, stream)
+                if int(self.n_redrawn.item()) == 0:
+                    return
+            else:
+                again = (sp.is_global == 0) & (prior_prop[:n] == SENTINEL)
+                k = int(again.sum().item())
+                if k == 0:
+                    return
+                sp.theta_prop[:n][again] = self.local_cb.sample(k) + sp.chains.theta.t()[again]
+            prior_prop[:n] = sp.model.prior(sp.theta_prop[:n])
+        raise RuntimeError("the local proposal keeps landing where prior_log_prob returns the sentinel "
+                           "7*log(1e-10) (GLMCMC.py:92-93) after %d redraws" % self.max_redraws)
+
+
+def replay_segments(start, num_ite, capture, snapshot, restore, violations, speculative, max_graph_rounds, segment=64):
+    """Iterations start .. num_ite-1 as replays of one captured iteration, decided by integers and callables only.
+    capture(i, rounds) runs iteration i (the warm-up of the capture IS iteration i of the chains) and returns a graph whose
+    replay() runs the next iteration, or None when the iteration cannot be captured.
+
+    Without a sentinel check (GlobalMCMC, sentinel_redraw=False) an iteration never visits the host and that is all.  WITH it
+    (`speculative`, the default for GLMCMC) almost no prior ever returns the sentinel, so the first capture holds no redraw
+    round at all and only counts the local candidates that hit it; violations() -- a synchronisation -- reads the count once per
+    `segment` iterations.  When it is non-zero, restore() brings back the state snapshot() took at the segment's start and the
+    iteration is captured AGAIN with 2, 4, ... max_graph_rounds redraw rounds inside the graph: a Model whose prior does return
+    the sentinel keeps running as a replayed graph.  Only a prior that still returns it after max_graph_rounds redraws of one
+    candidate, or a capture that fails, sends the rest of the run through the eager loop.  The Philox draws depend on (chain,
+    iteration, round) only, so every form gives the eager loop's chains.
+
+    Returns (the iteration the eager loop continues from, redraw rounds in the last graph, the iteration first rolled back to
+    or None, whether the run stayed a graph to its end)."""
+    i, rounds, rolled_back_at = start, 0, None
+    snapshot()
+    g = capture(i, rounds)
+    done = 1                                               # the warm-up iteration belongs to its segment
+    while g is not None:
+        k = min(segment - done, num_ite - i - done)
+        for _ in range(k):
+            g.replay()
+        if speculative and violations() != 0:
+            restore()                                      # back to iteration i
+            if rolled_back_at is None:
+                rolled_back_at = i
+            rounds = max(2, 2 * rounds)
+            if rounds > max_graph_rounds:
+                return i, rounds, rolled_back_at, False
+            g = capture(i, rounds)
+            done = 1
+            continue
+        i += done + k
+        done = 0
+        if i >= num_ite:
+            return num_ite, rounds, rolled_back_at, True
+        if speculative:
+            snapshot()
+    restore()                                              # a failed capture may have run part of an iteration
+    return i, rounds, rolled_back_at, False
+
+
+def _copy_all(dst, src):
+    for a, b in zip(dst, src):
+        a.copy_(b)
+
+
 def run(algo, ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Global_Proposal, filelocation, global_frequency,
         batch_size, csv_variant, *, seed=None, device=None, chain0=0, record_history=True, stats=None, return_device=False,
         verbose=True, state_out=None, callback_device="auto", sentinel_redraw=True, max_redraws=100000, max_graph_rounds=32,
@@ -197,251 +441,80 @@ def run(algo, ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Global_
     tensors, no sentinel check (GlobalMCMC, or sentinel_redraw=False) -- is captured ONCE as a hipGraph (torch.cuda.graph:
     the two HIP kernels with the iteration index in device memory, glabc_run.step0_device, plus the Model's own kernels) and
     replayed; 'auto' falls back to launching eagerly when the capture is not possible (e.g. a callback that synchronises).
-    With the sentinel check on (GLMCMC's default) the replay is speculative, see below: same results as the eager loop; a prior
-    that does return the sentinel keeps the run a replayed graph, with up to max_graph_rounds redraw rounds inside it."""
-    lib = _capi.lib()
-    dev, chains, single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
-    n, d, yd = chains.n, chains.d, chains.yd
+    With the sentinel check on (GLMCMC's default) the replay is speculative, see replay_segments: same results as the eager
+    loop; a prior that does return the sentinel keeps the run a replayed graph, with up to max_graph_rounds redraw rounds
+    inside it."""
     N = int(batch_size) if algo == _capi.ALGO_GLMCMC else 1
     if N < 1:
         raise ValueError("batch_size must be >= 1")
-    key = engine.draw_seed(seed)
-    model = ModelCallbacks(ABCset, dev, callback_device)
-    local_desc = dist_descriptor(Local_Proposal, d) if Local_Proposal is not None else None
-    global_desc = dist_descriptor(Global_Proposal, d, gamma=True)
-    local_cb = ProposalCallbacks(Local_Proposal, dev) if (local_desc is None and Local_Proposal is not None) else None
-    global_cb = ProposalCallbacks(Global_Proposal, dev) if global_desc is None else None
+    sp = SplitPhase(ABCset, num_ite, Initial_theta, Initial_y, device, chain0, seed, N, global_frequency, callback_device,
+                    record_history, stats)
+    step = Iteration(sp, algo, Local_Proposal, Global_Proposal, sentinel_redraw, max_redraws)
     if Local_Proposal is None and float(global_frequency) < 1:
         raise ValueError("a local proposal is needed unless global_frequency >= 1")
-
-    R = N * n
-    f32 = dict(dtype=torch.float32, device=dev)
-    theta_prop = torch.zeros(R, d, **f32)
-    log_q = torch.zeros(R, **f32)
-    nd = model.noise_dim
-    sim_noise = torch.zeros(R, nd, **f32) if nd else None
-    log_u = torch.zeros(n, **f32)
-    u_res = torch.zeros(n, dtype=torch.float64, device=dev)
-    is_global = torch.zeros(n, dtype=torch.int32, device=dev)
-    n_redrawn = torch.zeros(1, dtype=torch.int32, device=dev)
-    model.probe(chains.theta.t(), chains.y.t())
-    # callbacks of the initial state (GLMCMC.py:52-55): carried from here on by glabc_select
-    prior_cur = model.prior(chains.theta.t().contiguous()).clone()
-    kern_cur = model.kernel(chains.y.t().contiguous()).clone()
-    hist = _host.allocate_history(num_ite, chains, record_history)
-
-    io = _capi.StepIO()
-    io.n_prop, io.theta_dim, io.y_dim, io.noise_dim = N, d, yd, nd
-    io.theta_prop, io.log_q = theta_prop.data_ptr(), log_q.data_ptr()
-    io.sim_noise = sim_noise.data_ptr() if nd else None
-    io.log_u, io.u_res, io.is_global = log_u.data_ptr(), u_res.data_ptr(), is_global.data_ptr()
-    io.prior_cur, io.kern_cur = prior_cur.data_ptr(), kern_cur.data_ptr()
-    cs = chains.struct()
-    ms = stats.struct() if stats is not None else None
-    run_ = _capi.Run()
-    run_.seed, run_.n_steps, run_.global_frequency, run_.batch_size, run_.hist_stride = key, 1, float(global_frequency), N, n
-    if ms is not None:
-        run_.moments = C.pointer(ms)
-    hist_ptr, hist_row_bytes = (hist.data_ptr(), hist[0].numel() * 4) if hist is not None else (0, 0)
-    lp = C.byref(local_desc) if local_desc is not None else None
-    gp = C.byref(global_desc) if global_desc is not None else None
-
-    col_index = torch.arange(n, device=dev).view(1, n)
-    n_valid = torch.full((n,), N, dtype=torch.int32, device=dev)
-    if global_cb is not None and algo == _capi.ALGO_GLMCMC:
-        io.n_valid = n_valid.data_ptr()
-    keep = {}                                              # tensors whose addresses the current StepIO holds
-    speculating = [False]                                  # inside a captured iteration: bounded redraw rounds + a count
-    graph_rounds = [0]                                     # redraw rounds (GLMCMC.py:92-93) held by the captured iteration
-
-    def iteration(i):
-        """one iteration on torch's current stream; i = None: the index is read from step_t on the device (graph)"""
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if i is not None:
-            run_.step0 = i
-            run_.history = hist_ptr + i * hist_row_bytes if hist is not None else None
-        _capi.check(lib.glabc_propose(algo, lp, gp, C.byref(cs), C.byref(run_), C.byref(io), stream), "glabc_propose")
-        if global_cb is not None or local_cb is not None:
-            glob_rows = (is_global != 0)
-            if global_cb is not None:                                  # Importance_Proposal.forward(batch_size), GLMCMC.py:66
-                z, lq = global_cb.forward(R)
-                if local_cb is None:                                   # keep the kernel's local-move rows
-                    keep_rows = torch.zeros(R, dtype=torch.bool, device=dev)
-                    keep_rows[:n] = ~glob_rows
-                    z = torch.where(keep_rows.view(-1, 1), theta_prop, z)
-                theta_prop.copy_(z)
-                log_q.copy_(lq)
-                if algo == _capi.ALGO_GLMCMC:
-                    # GLMCMC.py:67-70: proposals with a NaN coordinate are dropped BEFORE the Model sees them; the weight vector
-                    # is then shorter.  Only a callback proposal can produce them.  Stays on the device: the chain's valid rows
-                    # move to the front in their order (the k-th survivor is simulated with the k-th noise row, as the
-                    # reference's generate_samples(Theta_prop0) draws for the shortened batch), glabc_select gets the count.
-                    bad = torch.isnan(theta_prop).any(1).view(N, n) & glob_rows.view(1, n)
-                    order = torch.argsort(bad.to(torch.uint8), dim=0, stable=True)
-                    rows = (order * n + col_index).view(-1)
-                    theta_prop.copy_(theta_prop[rows])
-                    log_q.copy_(log_q[rows])
-                    n_valid.copy_((N - bad.sum(0)).to(torch.int32))
-            if local_cb is not None:                                   # Local_Proposal.sample(1) + Theta_old, GLMCMC.py:91
-                row0_local = local_cb.sample(n) + chains.theta.t()
-                theta_prop[:n] = torch.where(glob_rows.view(-1, 1), theta_prop[:n], row0_local)
-        prior_prop = model.prior(theta_prop)                           # GLMCMC.py:74,92,96
-        io.prior_prop = prior_prop.data_ptr()
-        if sentinel_redraw and algo == _capi.ALGO_GLMCMC and speculating[0]:
-            # captured form: the reference's loop (GLMCMC.py:92-93) ends on a host read, which a hipGraph cannot hold, so the
-            # capture holds a BOUNDED number of its rounds -- redraw the local candidates whose prior is the sentinel (a
-            # round without one is a no-op: the kernel touches nothing and the prior of an unchanged row is the same number),
-            # evaluate the prior again -- and one more launch of the redraw kernel that only COUNTS the candidates still at the
-            # sentinel after them (its device counter is never zeroed here).  The replay loop below reads the count once per
-            # segment; if it is ever non-zero it restores the segment's start state and captures again with more rounds.
-            for rnd in range(1, graph_rounds[0] + 1):
-                _capi.check(lib.glabc_propose_redraw(lp, C.byref(cs), C.byref(run_), C.byref(io), rnd, n_redrawn.data_ptr(),
-                                                     stream), "glabc_propose_redraw")
-                prior_prop[:n] = model.prior(theta_prop[:n])
-            _capi.check(lib.glabc_propose_redraw(lp, C.byref(cs), C.byref(run_), C.byref(io), graph_rounds[0] + 1,
-                                                 violations.data_ptr(), stream), "glabc_propose_redraw")
-        elif sentinel_redraw and algo == _capi.ALGO_GLMCMC:            # GLMCMC.py:92-93
-            for rnd in range(1, max_redraws + 1):
-                if local_cb is None:
-                    n_redrawn.zero_()
-                    _capi.check(lib.glabc_propose_redraw(lp, C.byref(cs), C.byref(run_), C.byref(io), rnd,
-                                                         n_redrawn.data_ptr(), stream), "glabc_propose_redraw")
-                    if int(n_redrawn.item()) == 0:
-                        break
-                    prior_prop[:n] = model.prior(theta_prop[:n])
-                else:
-                    again = (is_global == 0) & (prior_prop[:n] == SENTINEL)
-                    k = int(again.sum().item())
-                    if k == 0:
-                        break
-                    theta_prop[:n][again] = local_cb.sample(k) + chains.theta.t()[again]
-                    prior_prop[:n] = model.prior(theta_prop[:n])
-            else:
-                raise RuntimeError("the local proposal keeps landing where prior_log_prob returns the sentinel "
-                                   "7*log(1e-10) (GLMCMC.py:92-93) after %d redraws" % max_redraws)
-        y_prop = model.simulate(theta_prop, sim_noise)                 # GLMCMC.py:71,94
-        if y_prop.shape[1] != yd:
-            raise ValueError("generate_samples returned %d columns, Initial_y has %d" % (y_prop.shape[1], yd))
-        kern_prop = model.kernel(y_prop)                               # GLMCMC.py:72,96
-        io.y_prop, io.kern_prop = y_prop.data_ptr(), kern_prop.data_ptr()
-        keep.update(prior=prior_prop, y=y_prop, kern=kern_prop)
-        if global_cb is not None:                                      # Importance_Proposal.log_prob(Theta_old), GLMCMC.py:63
-            keep["q"] = global_cb.log_prob(chains.theta.t().contiguous())
-            io.q_cur = keep["q"].data_ptr()
-        _capi.check(lib.glabc_select(algo, gp, C.byref(cs), C.byref(run_), C.byref(io), stream), "glabc_select")
-
-    # Graph replay.  Without a sentinel check (GlobalMCMC, sentinel_redraw=False) an iteration never visits the host.  WITH it
-    # (the default for GLMCMC) the replay is speculative: almost no prior ever returns the sentinel, so the first capture holds
-    # no redraw round at all and only counts the local candidates that hit it; the count is read once per segment of 64
-    # iterations.  When it is non-zero the segment's start state is restored and the iteration is captured AGAIN with 2, 4, ...
-    # max_graph_rounds redraw rounds inside the graph (device side, no host read): a Model whose prior does return the sentinel
-    # keeps running as a replayed graph.  Only a prior that still returns it after max_graph_rounds redraws of one candidate sends
-    # the rest of the run through the eager loop.  The Philox draws depend on (chain, iteration, round) only, so every form gives
-    # the eager path's chains.
-    plain = local_cb is None and global_cb is None and progress is None
-    speculative = plain and sentinel_redraw and algo == _capi.ALGO_GLMCMC
-    capturable = plain
-    if graph is True and not capturable:
+    dev, chains = sp.dev, sp.chains
+    plain = step.local_cb is None and step.global_cb is None and progress is None
+    speculative = plain and step.redraw
+    if graph is True and not plain:
         raise ValueError("graph=True needs descriptor proposals and no progress callback")
-    use_graph = capturable and graph in ("auto", True) and num_ite > 8
-    violations = torch.zeros(1, dtype=torch.int32, device=dev)
+    use_graph = plain and graph in ("auto", True) and num_ite > 8
     with torch.cuda.device(dev):
         i = 1
         if use_graph:
             # three eager iterations (they also settle where the callbacks run), then one captured iteration replayed
-            for _ in range(3):
-                iteration(i)
-                i += 1
-            use_graph = model.where != "cpu"
+            for i in (1, 2, 3):
+                step(i)
+            i = 4
+            use_graph = sp.model.where != "cpu"
         if use_graph:
-            saved = [t.clone() for t in (chains.theta, chains.y, chains.log_w, chains.flags, chains.n_moves, prior_cur, kern_cur)]
-            live = [chains.theta, chains.y, chains.log_w, chains.flags, chains.n_moves, prior_cur, kern_cur]
-            if stats is not None:
+            live = [chains.theta, chains.y, chains.log_w, chains.flags, chains.n_moves, sp.prior_cur, sp.kern_cur]
+            if stats is not None:                                               # a rolled-back segment has added to the sums
                 live += [stats.sum_theta, stats.sum_outer, stats.sum_jump]
-                saved += [t.clone() for t in (stats.sum_theta, stats.sum_outer, stats.sum_jump)]
-
-            def snapshot():
-                for a_, b_ in zip(saved, live):
-                    a_.copy_(b_)
-
-            def restore():
-                for a_, b_ in zip(saved, live):
-                    b_.copy_(a_)
-
-            step_t = torch.tensor([i], dtype=torch.int32, device=dev)          # the iteration index, on the device
+            saved = [t.clone() for t in live]
+            violations = torch.zeros(1, dtype=torch.int32, device=dev)
+            step_t = torch.tensor([i], dtype=torch.int32, device=dev)           # the iteration index, on the device
             side = torch.cuda.Stream(dev)
 
-            def capture():
-                """one iteration (graph_rounds[0] redraw rounds inside) as a hipGraph reading its index from step_t; the
-                warm-up run of the captured form IS iteration i of the chains.  None when it cannot be captured."""
-                step_t.fill_(i)
+            def capture(at, rounds):
+                """iteration `at` (`rounds` redraw rounds inside) warmed on a side stream, then captured as a hipGraph that
+                reads its index from step_t; None when it cannot be captured"""
+                step_t.fill_(at)
                 violations.zero_()
-                run_.step0, run_.step0_device = 1, step_t.data_ptr()
-                run_.history = hist_ptr + hist_row_bytes if hist is not None else None   # row 0 of `history` = iteration 1
-                g_ = torch.cuda.CUDAGraph()
+                sp.at(1)                                                        # row 0 of `history` = iteration 1
+                sp.run_.step0_device = step_t.data_ptr()
+                g = torch.cuda.CUDAGraph()
                 try:
                     side.wait_stream(torch.cuda.current_stream(dev))
                     with torch.cuda.stream(side):                               # warm the captured form once (step_t advances)
-                        iteration(None)
+                        step(None, rounds, violations if speculative else None)
                         step_t.add_(1)
                     torch.cuda.current_stream(dev).wait_stream(side)
-                    with torch.cuda.graph(g_):
-                        iteration(None)
+                    with torch.cuda.graph(g):
+                        step(None, rounds, violations if speculative else None)
                         step_t.add_(1)
                 except Exception:                                               # not capturable after all: launch eagerly
                     if graph is True:
                         raise
                     torch.cuda.synchronize(dev)
-                    g_ = None
+                    g = None
                 finally:
-                    run_.step0_device = None
-                return g_
+                    sp.run_.step0_device = None
+                return g
 
-            speculating[0] = speculative
-            snapshot()
-            g = capture()
-            done = 1 if g is not None else 0                                    # the warm-up iteration belongs to the first segment
-            if g is None:                                                       # (a failed capture may have run part of an iteration)
-                restore()
-            while g is not None and i + done <= num_ite:
-                k = min(64 - done, num_ite - i - done)
-                for _ in range(k):
-                    g.replay()
-                done += k
-                if speculative and int(violations.item()) != 0:                 # one synchronisation per segment
-                    restore()                                                   # back to iteration i
-                    if state_out is not None:
-                        state_out.setdefault("graph_rolled_back_at", i)
-                    graph_rounds[0] = max(2, 2 * graph_rounds[0])
-                    if graph_rounds[0] > max_graph_rounds:
-                        g = None
-                        break
-                    g = capture()
-                    done = 1 if g is not None else 0
-                    if g is None:
-                        restore()
-                    continue
-                i += done
-                done = 0
-                if i >= num_ite:
-                    break
-                if speculative:
-                    snapshot()
-            speculating[0] = False
-            if g is not None:
-                i = num_ite
-                if state_out is not None:
-                    state_out["graph"] = True
-                    state_out["graph_redraw_rounds"] = graph_rounds[0]
+            i, rounds, rolled_back_at, stayed_graph = replay_segments(
+                i, num_ite, capture, lambda: _copy_all(saved, live), lambda: _copy_all(live, saved),
+                lambda: int(violations.item()), speculative, max_graph_rounds)
+            if state_out is not None and rolled_back_at is not None:
+                state_out.setdefault("graph_rolled_back_at", rolled_back_at)
+            if state_out is not None and stayed_graph:
+                state_out.update(graph=True, graph_redraw_rounds=rounds)
         for i in range(i, num_ite):
-            iteration(i)
+            step(i)
             if progress is not None:
                 progress(i)
-    if stats is not None:
-        stats.steps += num_ite - 1
     if state_out is not None:
-        state_out.update(chains=chains, prior_cur=prior_cur, kern_cur=kern_cur, callback_device=model.where)
-    return _host.finish(hist, chains, single, filelocation, csv_variant, verbose and single, return_device)
+        state_out.update(chains=chains, prior_cur=sp.prior_cur, kern_cur=sp.kern_cur, callback_device=sp.model.where)
+    return sp.finish(filelocation, csv_variant, verbose, return_device)
 
 
 # ------------------------------------------------------------------------------------------- pool samplers (GLMCMC_NF, AGLMCMC)
@@ -457,58 +530,30 @@ def _noise_seed(key, chain0):
     return (int(key) ^ z) & 0x7FFFFFFFFFFFFFFF
 
 
-class PoolSampler:
+class PoolSampler(SplitPhase):
     """One chain-state + iteration engine shared by the callback forms of GLMCMC_NF and AGLMCMC: every chain owns a pool of
     P = batch_size*step_size proposals (row r = p*n + c), a global move is the iSIR step against the chain's next slice
     (GLMCMC_NFs.py:90-111 / AGLMCMC.py:125-172), a local move the random-walk MH step (:142-152 / :251-272).  The Model's
     methods evaluate a pool once (`load_pool`) and the local-move candidates every iteration; glabc_propose draws, glabc_select
-    decides.  `log_q_old` (the proposal's log-density of the current states) is the caller's to keep current."""
+    decides.  `log_q_old` (the proposal's log-density of the current states) is the caller's to keep current.  The history is
+    always recorded, and every launch goes to the stream that was current at construction."""
 
     def __init__(self, ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, global_frequency, step_size, batch_size,
                  seed, device, chain0, callback_device):
-        self.lib = _capi.lib()
-        self.dev, self.chains, self.single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
-        dev, chains = self.dev, self.chains
-        self.n, self.d, self.yd = chains.n, chains.d, chains.yd
-        n, d = self.n, self.d
-        self.N, self.S = int(batch_size), int(step_size)
+        super().__init__(ABCset, num_ite, Initial_theta, Initial_y, device, chain0, seed, batch_size, global_frequency,
+                         callback_device, True, None)
+        dev, n = self.dev, self.n
+        self.S = int(step_size)
         self.rows = self.N * self.S * n
-        R = self.N * n
-        self.key = engine.draw_seed(seed)
-        self.model = ModelCallbacks(ABCset, dev, callback_device)
-        self.local_desc = dist_descriptor(Local_Proposal, d)
+        self.local_desc = dist_descriptor(Local_Proposal, self.d)
         self.local_cb = ProposalCallbacks(Local_Proposal, dev) if self.local_desc is None else None
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(_noise_seed(self.key, chain0))
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.theta_prop = torch.zeros(R, d, **f32)
-        self.log_q = torch.zeros(R, **f32)
-        self.nd = self.model.noise_dim
-        self.sim_noise = torch.zeros(R, self.nd, **f32) if self.nd else None
-        self.log_u = torch.zeros(n, **f32)
-        self.u_res = torch.zeros(n, dtype=torch.float64, device=dev)
-        self.is_global = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.model.probe(chains.theta.t(), chains.y.t())
-        self.prior_cur = self.model.prior(chains.theta.t().contiguous()).clone()
-        self.kern_cur = self.model.kernel(chains.y.t().contiguous()).clone()
-        self.hist = _host.allocate_history(num_ite, chains, True)
         self.kk = torch.zeros(n, dtype=torch.int64, device=dev)
-        self.log_q_old = torch.zeros(n, **f32)
+        self.log_q_old = torch.zeros(n, dtype=torch.float32, device=dev)
         self._chain_ids = torch.arange(n, device=dev).view(1, n)
         self._slot = torch.arange(self.N, device=dev).view(self.N, 1)
         self.pool = {}
-        io = self.io = _capi.StepIO()
-        io.n_prop, io.theta_dim, io.y_dim, io.noise_dim = self.N, d, self.yd, self.nd
-        io.theta_prop, io.log_q = self.theta_prop.data_ptr(), self.log_q.data_ptr()
-        io.sim_noise = self.sim_noise.data_ptr() if self.nd else None
-        io.log_u, io.u_res, io.is_global = self.log_u.data_ptr(), self.u_res.data_ptr(), self.is_global.data_ptr()
-        io.prior_cur, io.kern_cur = self.prior_cur.data_ptr(), self.kern_cur.data_ptr()
-        self.cs = chains.struct()
-        run_ = self.run_ = _capi.Run()
-        run_.seed, run_.n_steps, run_.global_frequency, run_.batch_size, run_.hist_stride = \
-            self.key, 1, float(global_frequency), self.N, n
-        self._hist_ptr, self._hist_row_bytes = self.hist.data_ptr(), self.hist[0].numel() * 4
-        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         self._countdown = self.S
         self.group = None
 
@@ -528,11 +573,9 @@ class PoolSampler:
 
     def step(self, i):
         """iteration i for every chain; returns the mask of the chains that moved (on the device)"""
-        lib, n, N, io, run_, pool, chains = self.lib, self.n, self.N, self.io, self.run_, self.pool, self.chains
-        run_.step0, run_.history = i, self._hist_ptr + i * self._hist_row_bytes
-        lp = C.byref(self.local_desc) if self.local_desc is not None else None
-        _capi.check(lib.glabc_propose(_capi.ALGO_GLMCMC, lp, None, C.byref(self.cs), C.byref(run_), C.byref(io), self.stream),
-                    "glabc_propose")                                                            # branch, uniforms, local candidates
+        n, N, pool, chains = self.n, self.N, self.pool, self.chains
+        self.at(i)
+        self.propose(_capi.ALGO_GLMCMC, self.local_desc, None)                                    # branch, uniforms, local candidates
         glob = (self.is_global & 1) != 0
         if self.local_cb is not None:
             self.theta_prop[:n] = self.local_cb.sample(n) + chains.theta.t()
@@ -548,10 +591,7 @@ class PoolSampler:
         kern_prop[:n] = torch.where(loc, self.model.kernel(y_loc), kern_prop[:n])
         self.log_q.copy_(pool["lq"][src])
         chains.flags.fill_(_capi.FLAG_LOCAL)        # the current state's weight is recomputed at every global move
-        io.y_prop, io.prior_prop, io.kern_prop = y_prop.data_ptr(), prior_prop.data_ptr(), kern_prop.data_ptr()
-        io.q_cur = self.log_q_old.data_ptr()
-        _capi.check(lib.glabc_select(_capi.ALGO_GLMCMC, None, C.byref(self.cs), C.byref(run_), C.byref(io), self.stream),
-                    "glabc_select")
+        self.select(_capi.ALGO_GLMCMC, None, prior_prop, y_prop, kern_prop, self.log_q_old)
         self.kk += glob
         self._countdown -= 1
         return (self.is_global & 2) != 0
@@ -570,9 +610,6 @@ class PoolSampler:
             self._countdown = self.S - used
             return False
         return True
-
-    def finish(self, filelocation, csv_variant, verbose, return_device):
-        return _host.finish(self.hist, self.chains, self.single, filelocation, csv_variant, verbose and self.single, return_device)
 
 
 def run_glmcmc_nf(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, filelocation, global_frequency, step_size,
@@ -661,7 +698,7 @@ def run_aglmcmc(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Initi
         raise TypeError("AGLMCMC needs Model.discrepancy (AGLMCMC.py:93)")
     isir = ProposalCallbacks(Initial_ISIR_prop, dev)
     isir_desc = dist_descriptor(Initial_ISIR_prop, d)
-    drawn = [0]
+    draw_ids = itertools.count()
 
     def isir_forward():
         """Initial_ISIR_prop.forward(rows): on the device from the Philox stream when the proposal has a descriptor"""
@@ -670,23 +707,13 @@ def run_aglmcmc(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Initi
         z = torch.empty(d, rows, dtype=torch.float32, device=dev)
         lq = torch.empty(rows, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _capi.check(ps.lib.glabc_dist_forward(C.byref(isir_desc), rows, ps.key ^ 0x9E3779B97F4A7C15, (drawn[0] << 44) +
+            _capi.check(ps.lib.glabc_dist_forward(C.byref(isir_desc), rows, ps.key ^ 0x9E3779B97F4A7C15, (next(draw_ids) << 44) +
                                                   chains.chain0 * ps.N * ps.S, z.data_ptr(), lq.data_ptr(), ps.stream), "glabc_dist_forward")
-        drawn[0] += 1
         return z.t().contiguous(), lq
-
-    def discrepancy(y):
-        return model._call(lambda cuda: model._back(ABCset.discrepancy(y if cuda else y.cpu()), y.shape[0])).view(-1)
-
-    def kernel_of_discrepancy(dis, x, eps):                                                       # calculate_log_kernel_dis, :199
-        if hasattr(ABCset, "calculate_log_kernel_dis"):
-            return model._call(lambda cuda: model._back(ABCset.calculate_log_kernel_dis(dis if cuda else dis.cpu(), eps),
-                                                        dis.shape[0])).view(-1)
-        return model._call(lambda cuda: model._back(ABCset.calculate_log_kernel(x if cuda else x.cpu(), eps), x.shape[0])).view(-1)
 
     def load(theta_rows, lq):
         pool = ps.load_pool(theta_rows, lq)
-        pool["dis"] = discrepancy(pool["x"])                                                      # :93 / 236
+        pool["dis"] = model.discrepancy(pool["x"])                                                      # :93 / 236
 
     th, lq = isir_forward()                                                                       # :80-81
     load(th, lq)
@@ -713,7 +740,7 @@ def run_aglmcmc(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Initi
                         valid = valid[:: (valid.numel() >> 24) + 1]
                     hat_eps = float(torch.quantile(valid, q))
                 hat_eps = max(hat_eps, float(hat_eps_T))
-            tw = torch.exp(pool["prior"] + kernel_of_discrepancy(dis0, pool["x"], hat_eps) - pool["lq"])   # :199-202
+            tw = torch.exp(pool["prior"] + model.kernel_of_discrepancy(dis0, pool["x"], hat_eps) - pool["lq"])   # :199-202
             tw = torch.where(torch.isnan(tw), torch.zeros_like(tw), tw)
             cap = rows if (max_train is None and n == 1) else int(8192 if max_train is None else max_train)
             if cap < rows and not warned:
@@ -789,74 +816,36 @@ def run_glmala(ABCset, num_ite, Initial_theta, Initial_y, tau, num_grad, fileloc
     start from it -- `z*tau + Theta_old` is a float32 addition before the switch and a float64 one after, as in the fused
     kernel (GLABC_FLAG_TH64).  Theta_Re is float32 in either case (GLMALA.py:148,200).  y_old is not kept in double: it enters
     only through calculate_log_kernel(y_old), which is carried from the iteration that proposed it."""
-    lib = _capi.lib()
-    dev, chains, single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
-    n, d, yd = chains.n, chains.d, chains.yd
-    N = int(batch_size)
-    key = engine.draw_seed(seed)
-    model = ModelCallbacks(ABCset, dev, callback_device)
     if not hasattr(ABCset, "discrepancy"):
         raise TypeError("GLMALA needs Model.discrepancy (GLMALA.py:78)")
+    sp = SplitPhase(ABCset, num_ite, Initial_theta, Initial_y, device, chain0, seed, batch_size, global_frequency,
+                    callback_device, record_history, stats)
+    dev, chains, model, n, d, nd = sp.dev, sp.chains, sp.model, sp.n, sp.d, sp.nd
+    theta_prop, log_q, is_global = sp.theta_prop, sp.log_q, sp.is_global
     global_desc = dist_descriptor(Importance_Proposal, d, gamma=True)
     global_cb = ProposalCallbacks(Importance_Proposal, dev) if global_desc is None else None
     tau = float(tau)
     eps_sq = float(ABCset.epsilon) ** 2                                                          # GLMALA.py:90
     gen = torch.Generator(device=dev)
-    gen.manual_seed(_noise_seed(key, chain0))
-    host_rng = np.random.Generator(np.random.PCG64(_noise_seed(key, chain0)))
-
-    def discrepancy(y):
-        return model._call(lambda cuda: model._back(ABCset.discrepancy(y if cuda else y.cpu()), y.shape[0])).view(-1)
-    model.discrepancy = discrepancy
-
-    R = N * n
-    f32 = dict(dtype=torch.float32, device=dev)
-    theta_prop = torch.zeros(R, d, **f32)
-    log_q = torch.zeros(R, **f32)
-    nd = model.noise_dim
-    sim_noise = torch.zeros(R, nd, **f32) if nd else None
-    log_u = torch.zeros(n, **f32)
-    u_res = torch.zeros(n, dtype=torch.float64, device=dev)
-    is_global = torch.zeros(n, dtype=torch.int32, device=dev)
-    model.probe(chains.theta.t(), chains.y.t())
-    prior_cur = model.prior(chains.theta.t().contiguous()).clone()
-    kern_cur = model.kernel(chains.y.t().contiguous()).clone()
+    gen.manual_seed(_noise_seed(sp.key, chain0))
+    host_rng = np.random.Generator(np.random.PCG64(_noise_seed(sp.key, chain0)))
     grad = torch.zeros(n, d, dtype=torch.float64, device=dev)                                    # grad_logABC_Theta_old, :146
     has_grad = torch.zeros(n, dtype=torch.bool, device=dev)
     theta64 = chains.theta.t().double().contiguous()                                             # Theta_old, (n, d)
     th64 = torch.zeros(n, dtype=torch.bool, device=dev)                                          # ... is a float64 tensor
-    hist = _host.allocate_history(num_ite, chains, record_history)
-
-    io = _capi.StepIO()
-    io.n_prop, io.theta_dim, io.y_dim, io.noise_dim = N, d, yd, nd
-    io.theta_prop, io.log_q = theta_prop.data_ptr(), log_q.data_ptr()
-    io.sim_noise = sim_noise.data_ptr() if nd else None
-    io.log_u, io.u_res, io.is_global = log_u.data_ptr(), u_res.data_ptr(), is_global.data_ptr()
-    io.prior_cur, io.kern_cur = prior_cur.data_ptr(), kern_cur.data_ptr()
-    cs = chains.struct()
-    ms = stats.struct() if stats is not None else None
-    run_ = _capi.Run()
-    run_.seed, run_.n_steps, run_.global_frequency, run_.batch_size, run_.hist_stride = key, 1, float(global_frequency), N, n
-    if ms is not None:
-        run_.moments = C.pointer(ms)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    hist_ptr, hist_row_bytes = (hist.data_ptr(), hist[0].numel() * 4) if hist is not None else (0, 0)
-    gp = C.byref(global_desc) if global_desc is not None else None
     c_norm = -0.5 * d * math.log(2 * math.pi)
 
     with torch.cuda.device(dev):
         for i in range(1, num_ite):
-            run_.step0 = i
-            run_.history = hist_ptr + i * hist_row_bytes if hist is not None else None
-            _capi.check(lib.glabc_propose(_capi.ALGO_GLMALA, None, gp, C.byref(cs), C.byref(run_), C.byref(io), stream),
-                        "glabc_propose")
+            sp.at(i)
+            sp.propose(_capi.ALGO_GLMALA, None, global_desc)
             if global_cb is not None:                                                           # GLMALA.py:158
-                z, lq = global_cb.forward(R)
+                z, lq = global_cb.forward(sp.N * n)
                 theta_prop.copy_(z)
                 log_q.copy_(lq)
             # ---- iSIR candidates of every chain (rows of chains on the local branch are overwritten below) :158-165
             prior_prop = model.prior(theta_prop)
-            y_prop = model.simulate(theta_prop, sim_noise)
+            y_prop = model.simulate(theta_prop, sp.sim_noise)
             kern_prop = model.kernel(y_prop)
             # ---- MALA move of the chains on the local branch, GLMALA.py:182-200
             idx = torch.nonzero(is_global == 0).view(-1)
@@ -887,11 +876,8 @@ def run_glmala(ABCset, num_ite, Initial_theta, Initial_y, tau, num_grad, fileloc
                 prior_prop[idx] = model.prior(th_new)
                 kern_prop[idx] = model.kernel(y_new)
                 log_q[idx] = (rev - logq_fwd.double()).float()                                   # the proposal terms of :190-193
-            io.prior_prop, io.y_prop, io.kern_prop = prior_prop.data_ptr(), y_prop.data_ptr(), kern_prop.data_ptr()
-            if global_cb is not None:
-                q_cur = global_cb.log_prob(chains.theta.t().contiguous())
-                io.q_cur = q_cur.data_ptr()
-            _capi.check(lib.glabc_select(_capi.ALGO_GLMALA, gp, C.byref(cs), C.byref(run_), C.byref(io), stream), "glabc_select")
+            q_cur = global_cb.log_prob(chains.theta.t().contiguous()) if global_cb is not None else None
+            sp.select(_capi.ALGO_GLMALA, global_desc, prior_prop, y_prop, kern_prop, q_cur)
             gm = ((is_global & 1) != 0) & ((is_global & 2) != 0)                                 # an accepted iSIR move: a float32 candidate
             theta64[gm] = chains.theta.t()[gm].double()
             if L:                                                                                # :194-199
@@ -901,8 +887,6 @@ def run_glmala(ABCset, num_ite, Initial_theta, Initial_y, tau, num_grad, fileloc
                 th64[idx[moved]] = True
             if progress is not None:
                 progress(i)
-    if stats is not None:
-        stats.steps += num_ite - 1
     if state_out is not None:
         state_out.update(chains=chains, grad=grad, has_grad=has_grad, theta64=theta64, th64=th64, callback_device=model.where)
-    return _host.finish(hist, chains, single, filelocation, "global", verbose and single, return_device)
+    return sp.finish(filelocation, "global", verbose, return_device)
