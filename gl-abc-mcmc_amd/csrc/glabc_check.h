@@ -1,11 +1,12 @@
 // glabc_check.h -- the argument checks the entry points of include/glabc.h share, as pure functions of the descriptors
-// (no HIP: tests/test_arg_checks.py compiles this header with g++).  Each returns GLABC_OK or the status the entry point
+// (no HIP: tests/test_arg_checks.py compiles this header with g++; glabc_rtc_kernels.h is host only too).  Each returns GLABC_OK or the status the entry point
 // returns; an entry point calls them in the order its own contract lists the checks and keeps inline what only it asks.
 #pragma once
 
 #include <cmath>
 
 #include "../../include/glabc.h"
+#include "glabc_rtc_kernels.h"
 
 namespace glabc {
 
@@ -112,5 +113,33 @@ inline int check_lanes_wide(int lanes)
 }
 
 inline int check_lanes(int lanes) { return (lanes == 0 || lanes == 1 || lanes == 2 || lanes == 4) ? GLABC_OK : GLABC_ERR_ARG; }
+
+// ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------
+inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
+                         const glabc_run* r)
+{
+    if (!m || !c || !r) return GLABC_ERR_NULL;
+    if (m->sim_kind != GLABC_SIM_USER) return GLABC_ERR_KIND;
+    if (m->theta_dim != p.theta_dim || m->y_dim != p.y_dim || m->noise.dim != p.noise_dim) return GLABC_ERR_DIM;
+    // a Gamma prior / global proposal: where the program holds the Gamma kernels (GLABC_RTC_GAMMA); `local` never
+    const bool allow_gamma = p.gamma != 0;
+    if (check_dist(&m->prior, p.theta_dim, allow_gamma) || check_dist(local, p.theta_dim) || check_dist(global, p.theta_dim, allow_gamma))
+        return GLABC_ERR_ARG;                                     // whatever the defect of a descriptor
+    if (!std::isfinite(m->kern_log_scale) || !(m->kern_scale > 0.0f) || !std::isfinite(m->kern_c0)) return GLABC_ERR_ARG;
+    if (int e = check_chains(c, p.algo == GLABC_ALGO_GLMCMC ? CHAINS_ISIR : CHAINS_PLAIN)) return e;
+    if (r->n_steps < 0) return GLABC_ERR_ARG;
+    if (p.wide) {                                                 // lane groups: batch sizes the register kernels do not hold
+        if (r->batch_size <= GLABC_MAX_BATCH || r->batch_size > GLABC_MAX_BATCH_WIDE) return GLABC_ERR_ARG;
+        if (check_lanes_wide(r->lanes_per_chain) || r->tape || r->step0_device) return GLABC_ERR_ARG;
+    } else {
+        if (p.algo == GLABC_ALGO_GLMCMC && r->batch_size != p.batch_size) return GLABC_ERR_ARG;      // compiled for one batch size
+        if (r->tape || r->step0_device || (r->lanes_per_chain != 0 && r->lanes_per_chain != 1)) return GLABC_ERR_ARG;
+    }
+    if (r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
+    if (int e = check_frequency(r)) return e;
+    if (int e = check_history(r, c->n_chains)) return e;
+    if (int e = check_moments(r)) return e;
+    return check_step_counter(r);
+}
 
 }  // namespace glabc

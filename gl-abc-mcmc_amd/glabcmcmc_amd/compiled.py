@@ -108,21 +108,15 @@ class CompiledModel:
             handle = C.c_void_p()
             log = C.create_string_buffer(1 << 16)
             src = self.simulator_source.encode()
-            if gamma and wide:
+            flags = _capi.RTC_GAMMA if gamma else 0
+            if wide:
                 name = "glabc_rtc_compile_wide_ex"
-                rc = _capi.lib().glabc_rtc_compile_wide_ex(src, self.theta_dim, self.y_dim, self.noise_dim, _capi.RTC_GAMMA,
-                                                           C.byref(handle), log, len(log))
-            elif gamma:
-                name = "glabc_rtc_compile_ex"
-                rc = _capi.lib().glabc_rtc_compile_ex(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, _capi.RTC_GAMMA,
-                                                      C.byref(handle), log, len(log))
-            elif wide:
-                name = "glabc_rtc_compile_wide"
-                rc = _capi.lib().glabc_rtc_compile_wide(src, self.theta_dim, self.y_dim, self.noise_dim, C.byref(handle), log, len(log))
+                rc = _capi.lib().glabc_rtc_compile_wide_ex(src, self.theta_dim, self.y_dim, self.noise_dim, flags, C.byref(handle), log,
+                                                           len(log))
             else:
-                name = "glabc_rtc_compile"
-                rc = _capi.lib().glabc_rtc_compile(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, C.byref(handle), log,
-                                                   len(log))
+                name = "glabc_rtc_compile_ex"
+                rc = _capi.lib().glabc_rtc_compile_ex(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, flags, C.byref(handle),
+                                                      log, len(log))
             if rc != _capi.OK:
                 raise SimulatorCompileError("%s failed (status %d):\n%s" % (name, rc, log.value.decode(errors="replace")))
             self._programs[key] = handle

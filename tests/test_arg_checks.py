@@ -1,8 +1,8 @@
 """The argument checks the C ABI's entry points share (csrc/glabc_check.h), on the CPU.  The header is a set of pure functions
 of the descriptors of include/glabc.h, so a g++ driver evaluates them; the rows below say what each must answer.  They were
 written by hand from the checks the entry points carried before the header existed (check_dist / check_model / check_run /
-check_mala_chains of glabc_hip.hip, dist_ok of glabc_rtc.hip, pack_gen_dist / pack_common of glabc_generic.hip) and are never
-printed from the header: a status code is behaviour, a caller tells the defects apart by it.
+check_mala_chains of glabc_hip.hip, the checks glabc_rtc_steps of glabc_rtc.hip carried inline, pack_gen_dist / pack_common of
+glabc_generic.hip) and are never printed from the header: a status code is behaviour, a caller tells the defects apart by it.
 
 A row is (C++ statements that spoil the valid baseline `b`, expected status).  Every table starts from the untouched baseline,
 which must return GLABC_OK."""
@@ -92,30 +92,41 @@ int main()
 """
 
 
-def run_rows(tmp_path_factory, name, calls):
+def run_rows(tmp_path_factory, name, calls, flags=()):
     """calls: [(spoiling statements, expression)] -> the expressions' values, each evaluated on a fresh baseline"""
     d = tmp_path_factory.mktemp(name)
-    body = "".join("    { Base b; %s std::printf(\"%%d\\n\", (int)(%s)); }\n" % (spoil, expr) for spoil, expr in calls)
-    (d / "checks.cpp").write_text(PRELUDE + body + "    return 0;\n}\n")
-    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"),
+    # a function per row: a compiler, and a sanitizer's instrumentation above all, takes long over one function of hundreds of scopes
+    rows = "".join("static void row_%d() { Base b; %s std::printf(\"%%d\\n\", (int)(%s)); }\n" % (i, spoil, expr)
+                   for i, (spoil, expr) in enumerate(calls))
+    head, main = PRELUDE.split("int main()")
+    body = "".join("    row_%d();\n" % i for i in range(len(calls)))
+    (d / "checks.cpp").write_text(head + rows + "int main()" + main + body + "    return 0;\n}\n")
+    subprocess.check_call(["g++", "-std=c++17", *flags, "-I", os.path.join(ROOT, "include"),
                            "-I", os.path.join(ROOT, "gl-abc-mcmc_amd", "csrc"), str(d / "checks.cpp"), "-o", str(d / "checks")])
-    out = subprocess.run([str(d / "checks")], capture_output=True, text=True, check=True).stdout.split()
+    run = subprocess.run([str(d / "checks")], capture_output=True, text=True, check=True)
+    assert run.stderr == "", run.stderr                                    # a sanitizer's report
+    out = run.stdout.split()
     assert len(out) == len(calls)
     return [int(x) for x in out]
 
 
-def check_table(tmp_path_factory, name, rows):
+def check_table(tmp_path_factory, name, rows, flags=()):
     """rows: [(spoil, expression, expected)]"""
-    got = run_rows(tmp_path_factory, name, [(s, e) for s, e, _ in rows])
+    got = run_rows(tmp_path_factory, name, [(s, e) for s, e, _ in rows], flags)
     wrong = [(s, e, want, g) for (s, e, want), g in zip(rows, got) if g != want]
     assert not wrong, "(spoil, call, expected, returned): %r" % wrong
 
 
 def test_header_needs_no_hip(tmp_path_factory):
-    """glabc_check.h includes include/glabc.h and <cmath>, nothing else"""
-    src = open(os.path.join(ROOT, "gl-abc-mcmc_amd", "csrc", "glabc_check.h")).read()
-    includes = [line.split()[1] for line in src.splitlines() if line.startswith("#include")]
-    assert includes == ["<cmath>", '"../../include/glabc.h"']
+    """glabc_check.h includes include/glabc.h, <cmath> and the shape of a run-time compiled program, glabc_rtc_kernels.h; that
+    one the standard library and the two headers of integer rules, which include nothing but include/glabc.h"""
+    def includes(name):
+        src = open(os.path.join(ROOT, "gl-abc-mcmc_amd", "csrc", name)).read()
+        return [line.split()[1] for line in src.splitlines() if line.startswith("#include")]
+    assert includes("glabc_check.h") == ["<cmath>", '"../../include/glabc.h"', '"glabc_rtc_kernels.h"']
+    assert includes("glabc_rtc_kernels.h") == ["<cstdio>", "<string>", '"glabc_geometry.h"', '"glabc_plan.h"']
+    assert includes("glabc_plan.h") == ['"../../include/glabc.h"', '"glabc_geometry.h"']
+    assert includes("glabc_geometry.h") == ['"../../include/glabc.h"']
 
 
 # ---- glabc_dist ------------------------------------------------------------------------------------------------------------
@@ -376,3 +387,132 @@ def run_rows_table():
 
 def test_check_run(tmp_path_factory):
     check_table(tmp_path_factory, "run", run_rows_table())
+
+
+# ---- glabc_rtc_steps -------------------------------------------------------------------------------------------------------
+# the baseline as a launch of a run-time compiled program: the caller's simulator, a local and a global proposal, and the shape
+# the program was compiled for -- {algo, theta_dim, y_dim, noise_dim, batch_size, lanes, wide, gamma, hooks}
+RTC_BASE = ("b.m.sim_kind = GLABC_SIM_USER; glabc_dist lo = dist3(%s), gl = dist3(%s); " % (GAUSS, GAUSS) +
+            "RtcShape p = {GLABC_ALGO_GLMCMC, 3, 3, 3, 5, 1, 0, 0, 0}; ")
+RTC_CALL = "check_rtc_run(p, &b.m, &lo, &gl, &b.c, &b.r)"
+RTC_GLOBAL = "p.algo = GLABC_ALGO_GLOBALMCMC; p.batch_size = 1; "
+RTC_WIDE = "p.batch_size = 0; p.lanes = 0; p.wide = 1; b.r.batch_size = 17; "
+RTC_GAMMA = "p.gamma = 1; "
+
+
+def rtc_rows():
+    rows = []
+
+    def row(spoil, want, call=RTC_CALL):
+        rows.append((RTC_BASE + spoil, call, want))
+
+    def every_program(spoil, want):
+        for program in ("", RTC_GLOBAL, RTC_WIDE, RTC_GAMMA, RTC_WIDE + RTC_GAMMA, RTC_GLOBAL + RTC_GAMMA):
+            row(program + spoil, want)
+
+    every_program("", OK)
+    every_program("p.lanes = p.wide ? 0 : 4; p.hooks = 1;", OK)                 # neither is a matter of the launch
+    # null pointers first; a missing proposal is a defect of a descriptor
+    for call in ("check_rtc_run(p, nullptr, &lo, &gl, &b.c, &b.r)", "check_rtc_run(p, &b.m, &lo, &gl, nullptr, &b.r)",
+                 "check_rtc_run(p, &b.m, &lo, &gl, &b.c, nullptr)", "check_rtc_run(p, nullptr, nullptr, nullptr, nullptr, nullptr)"):
+        row("", NULL, call)
+        row("b.m.sim_kind = GLABC_SIM_GK; b.m.theta_dim = 2;", NULL, call)
+    row("", ARG, "check_rtc_run(p, &b.m, nullptr, &gl, &b.c, &b.r)")
+    row("", ARG, "check_rtc_run(p, &b.m, &lo, nullptr, &b.c, &b.r)")
+    row("b.m.theta_dim = 2;", DIM, "check_rtc_run(p, &b.m, nullptr, nullptr, &b.c, &b.r)")
+    # the caller's simulator, then the program's dimensions; the noise descriptor gives the normals per simulation and no more
+    every_program("b.m.sim_kind = GLABC_SIM_ABS_GAUSS;", KIND)
+    row("b.m.sim_kind = GLABC_SIM_GK;", KIND)
+    row("b.m.sim_kind = GLABC_SIM_ABS_GAUSS; b.m.theta_dim = 2;", KIND)
+    every_program("b.m.theta_dim = 2;", DIM)
+    row("b.m.y_dim = 2;", DIM)
+    row("b.m.noise.dim = 2;", DIM)
+    row("p.theta_dim = 4;", DIM)
+    row("p.y_dim = 4;", DIM)
+    row("p.noise_dim = 4;", DIM)
+    row("p.noise_dim = 2; b.m.noise.dim = 2;", OK)
+    row("b.m.noise.kind = 3; b.m.noise.p2[0] = NaN; b.m.noise.c0 = NaN; b.m.gk_c = NaN;", OK)
+    row("b.m.y_dim = 2; b.m.prior.p0[0] = NaN;", DIM)
+    # the prior, `local`, `global`: GLABC_ERR_ARG whatever check_dist finds
+    for d in ("b.m.prior", "lo", "gl"):
+        every_program(d + ".dim = 2;", ARG)                                     # check_dist: GLABC_ERR_DIM
+        every_program(d + ".kind = 3;", ARG)                                    # check_dist: GLABC_ERR_KIND
+        row(d + ".p0[0] = NaN;", ARG)
+        row(d + ".p0[3] = NaN;", OK)
+        row(d + ".c0 = Inf;", ARG)
+    row("b.m.prior.c0 = NaN;", ARG)                                             # a Uniform prior's constant
+    row("lo.p2[2] = 0.0f;", ARG)
+    row("b.m.prior.p2[2] = 0.0f;", OK)                                          # high - low of a Uniform: only finite
+    # a Gamma: the prior and the global proposal of a program that holds the Gamma kernels; `local` never
+    for program in ("", RTC_GLOBAL, RTC_WIDE):
+        for d in ("b.m.prior", "gl"):
+            row(program + d + " = dist3(%s);" % GAMMA, ARG)
+            row(program + RTC_GAMMA + d + " = dist3(%s);" % GAMMA, OK)
+            row(program + RTC_GAMMA + d + " = dist3(%s); %s.p1[1] = 0.0f;" % (GAMMA, d), ARG)
+        row(program + RTC_GAMMA + "b.m.prior = dist3(%s); gl = dist3(%s);" % (GAMMA, GAMMA), OK)
+        row(program + "lo = dist3(%s);" % GAMMA, ARG)
+        row(program + RTC_GAMMA + "lo = dist3(%s);" % GAMMA, ARG)
+    row("b.m.sim_kind = GLABC_SIM_GK; gl = dist3(%s);" % GAMMA, KIND)
+    # the ABC kernel: a finite log scale and constant, a scale above zero (an infinite one passes here); y_obs is not read
+    for spoil, want in (("b.m.kern_log_scale = NaN;", ARG), ("b.m.kern_log_scale = -Inf;", ARG), ("b.m.kern_scale = 0.0f;", ARG),
+                        ("b.m.kern_scale = -0.1f;", ARG), ("b.m.kern_scale = NaN;", ARG), ("b.m.kern_scale = Inf;", OK),
+                        ("b.m.kern_c0 = NaN;", ARG), ("b.m.kern_c0 = Inf;", ARG), ("b.m.y_obs[0] = NaN;", OK), ("b.m.epsilon = NaN;", OK)):
+        row(spoil, want)
+    row("gl.kind = 3; b.m.kern_scale = 0.0f; b.c.theta = nullptr;", ARG)
+    row("b.m.kern_scale = 0.0f; b.c.theta = nullptr;", ARG)                     # the kernel before the chains
+    # the chains: iSIR arrays for GLMCMC (register and wide), theta and y for GlobalMCMC
+    for program, required in (("", FORMS["CHAINS_ISIR"]), (RTC_WIDE, FORMS["CHAINS_ISIR"]), (RTC_GLOBAL, FORMS["CHAINS_PLAIN"])):
+        for ptr in POINTERS:
+            row(program + "b.c.%s = nullptr;" % ptr, NULL if ptr in required else OK)
+        for spoil, want in RANGE:
+            row(program + spoil, want)
+        row(program + "b.c.theta = nullptr; b.c.n_chains = -1;", NULL)
+        row(program + "b.c.y = nullptr; b.r.n_steps = -1;", NULL)               # the chains before n_steps
+        row(program + "b.r.n_steps = -1;", ARG)
+        row(program + "b.r.n_steps = 0;", OK)
+        row(program + "b.r.n_steps = -1; b.r.moments = &b.mo; b.mo.sum_jump = nullptr;", ARG)
+    # a wide program: batch sizes 17..4096, lane groups of 8 / 16 / 32 / 64, neither a tape nor a device step counter
+    for n, want in ((0, ARG), (5, ARG), (16, ARG), (17, OK), (64, OK), (4096, OK), (4097, ARG), (-1, ARG)):
+        row(RTC_WIDE + "b.r.batch_size = %d;" % n, want)
+        row(RTC_WIDE + RTC_GAMMA + "b.r.batch_size = %d;" % n, want)
+    for lanes in (-1, 0, 1, 2, 4, 7, 8, 9, 16, 32, 64, 65, 128):
+        row(RTC_WIDE + "b.r.lanes_per_chain = %d;" % lanes, OK if lanes in (0, 8, 16, 32, 64) else ARG)
+    # a register program: GLMCMC at the compiled batch size, GlobalMCMC at any; one lane per chain or the library's choice
+    for n, want in ((4, ARG), (5, OK), (6, ARG), (1, ARG), (16, ARG), (17, ARG), (0, ARG)):
+        row("b.r.batch_size = %d;" % n, want)
+    row("p.batch_size = 16; b.r.batch_size = 16;", OK)
+    row("p.batch_size = 16;", ARG)
+    for n in (0, 1, 5, 16, 17, 4097, -3):
+        row(RTC_GLOBAL + "b.r.batch_size = %d;" % n, OK)
+    for program in ("", RTC_GLOBAL, RTC_GAMMA):
+        for lanes in (-1, 0, 1, 2, 4, 8, 64):
+            row(program + "b.r.lanes_per_chain = %d;" % lanes, OK if lanes in (0, 1) else ARG)
+        row(program + "p.lanes = 2; b.r.lanes_per_chain = 2;", ARG)             # whatever the entry was compiled for
+    for program in ("", RTC_GLOBAL, RTC_WIDE):
+        row(program + "glabc_tape t = {}; b.r.tape = &t;", ARG)
+        row(program + "b.r.step0_device = b.u;", ARG)
+        # exact arithmetic only, and nowhere to write draws
+        row(program + "b.r.math_mode = GLABC_MATH_FAST;", ARG)
+        row(program + "b.r.math_mode = 2;", ARG)
+        row(program + "glabc_draws_out o = {}; b.r.dump_draws = &o;", ARG)
+        # what every stepping entry point asks, in its order: frequency, history, moments, step counter
+        row(program + "b.r.global_frequency = NaN;", ARG)
+        row(program + "b.r.global_frequency = Inf;", OK)
+        row(program + "b.r.history = b.f; b.r.hist_stride = 64;", ARG)
+        row(program + "b.r.history = b.f; b.r.hist_stride = 65;", OK)
+        row(program + "b.r.hist_stride = 64;", OK)
+        row(program + "b.r.moments = &b.mo;", OK)
+        for arr in ("sum_theta", "sum_outer", "sum_jump"):
+            row(program + "b.r.moments = &b.mo; b.mo.%s = nullptr;" % arr, NULL)
+        row(program + "b.r.step0 = 0xFFFFFFFEu; b.r.n_steps = 1;", OK)
+        row(program + "b.r.step0 = 0xFFFFFFFEu; b.r.n_steps = 2;", ARG)
+        row(program + "b.r.math_mode = GLABC_MATH_FAST; b.r.moments = &b.mo; b.mo.sum_jump = nullptr;", ARG)
+        row(program + "b.r.history = b.f; b.r.hist_stride = 64; b.r.moments = &b.mo; b.mo.sum_jump = nullptr;", ARG)
+        row(program + "b.r.moments = &b.mo; b.mo.sum_jump = nullptr; b.r.step0 = 0xFFFFFFFFu; b.r.n_steps = 1;", NULL)
+        row(program + "b.r.lanes_per_chain = 3; b.r.moments = &b.mo; b.mo.sum_jump = nullptr;", ARG)
+    return rows
+
+
+def test_check_rtc_run(tmp_path_factory):
+    """the statuses of glabc_rtc_steps; the table's driver is built with the address and undefined-behaviour sanitizers"""
+    check_table(tmp_path_factory, "rtc", rtc_rows(), flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
