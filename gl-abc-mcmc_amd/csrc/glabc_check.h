@@ -114,6 +114,56 @@ inline int check_lanes_wide(int lanes)
 
 inline int check_lanes(int lanes) { return (lanes == 0 || lanes == 1 || lanes == 2 || lanes == 4) ? GLABC_OK : GLABC_ERR_ARG; }
 
+// ---- glabc_mixture (include/glabc.h) ---------------------------------------------------------------------------------------------
+// dim: the dimension the caller expects, or 0 for any of 1..GLABC_MAX_DIM
+inline int check_mixture(const glabc_mixture* g, int dim)
+{
+    if (!g) return GLABC_ERR_NULL;
+    if (g->n_modes < 1 || g->n_modes > GLABC_MAX_MODES) return GLABC_ERR_ARG;
+    if (g->dim < 1 || g->dim > GLABC_MAX_DIM || (dim > 0 && g->dim != dim)) return GLABC_ERR_DIM;
+    for (int k = 0; k < g->n_modes; ++k) {
+        for (int q = 0; q < g->dim; ++q)
+            if (!std::isfinite(g->loc[k][q]) || !(g->scale[k][q] > 0.0) || !std::isfinite(g->scale[k][q]) ||
+                !(g->inv_scale[k][q] > 0.0) || !std::isfinite(g->inv_scale[k][q]))
+                return GLABC_ERR_ARG;
+        // log_weight may be -inf (a mode of weight 0), never NaN or +inf
+        if (!(g->log_weight[k] < INFINITY) || !std::isfinite(g->sum_log_scale[k])) return GLABC_ERR_ARG;
+        if (!(g->cum_weight[k] >= (k ? g->cum_weight[k - 1] : 0.0))) return GLABC_ERR_ARG;           // monotone, no NaN
+    }
+    const double last = g->cum_weight[g->n_modes - 1];
+    if (!(last > 0.0) || !(last <= 1.0 + 1e-9)) return GLABC_ERR_ARG;
+    return std::isfinite(g->c0) ? GLABC_OK : GLABC_ERR_ARG;
+}
+
+// glabc_glmcmc_mix_steps / glabc_globalmcmc_mix_steps: the support matrix of the mixture variant (include/glabc.h)
+inline int check_mix_model(const glabc_model* m, const glabc_mixture* g)
+{
+    if (int e = check_model(m, false, true)) return e;
+    if (m->prior.kind == GLABC_DIST_GAMMA) return GLABC_ERR_KIND;
+    if (m->sim_kind == GLABC_SIM_ABS_GAUSS && m->theta_dim > 4) return GLABC_ERR_KIND;               // instantiated up to 4, and g-and-k
+    return check_mixture(g, m->theta_dim);
+}
+
+inline int check_mix_run(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
+                         const glabc_run* r, bool isir)
+{
+    if (int e = check_mix_model(m, g)) return e;
+    if (int e = check_dist(local, m->theta_dim)) return e;
+    if (!c || !r) return GLABC_ERR_NULL;
+    if (r->tape) return GLABC_ERR_ARG;                          // a tape has no mode draws
+    if (int e = check_chains(c, isir ? CHAINS_ISIR : CHAINS_PLAIN)) return e;
+    if (r->n_steps < 0) return GLABC_ERR_ARG;
+    if (int e = check_frequency(r)) return e;
+    if (isir && (r->batch_size < 1 || r->batch_size > GLABC_MAX_BATCH)) return GLABC_ERR_ARG;
+    if (r->lanes_per_chain != 0 && r->lanes_per_chain != 1) return GLABC_ERR_ARG;
+    if (int e = check_history(r, c->n_chains)) return e;
+    if (int e = check_moments(r)) return e;
+    if (int e = check_step_counter(r)) return e;
+    if (r->step0_device) return GLABC_ERR_ARG;                  // the split-phase entry points only
+    if (r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------
 inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
                          const glabc_run* r)

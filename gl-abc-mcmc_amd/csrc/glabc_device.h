@@ -50,7 +50,9 @@ enum Algo { ALGO_GLMCMC = 0, ALGO_GLOBAL = 1 };
 // VAR_TAPE = VAR_GENERIC with the random numbers replayed from glabc_run.tape instead of Philox (one lane per chain).
 // VAR_GAMMA = VAR_GENERIC that also knows GLABC_DIST_GAMMA as the global / importance proposal and as the prior (one lane per
 // chain): its float64 log-density and Marsaglia-Tsang loop stay out of the other instantiations' register budgets.
-enum Variant { VAR_GENERIC = 0, VAR_GAUSS_UNIT = 1, VAR_TAPE = 2, VAR_GAMMA = 3 };
+// VAR_MIX = VAR_GENERIC whose global / importance proposal is a GaussianMixture (glabc_mixture, include/glabc.h; one lane per
+// chain): the mixture's tables follow the StepArgs in the argument block of these instantiations only (MixStepArgs).
+enum Variant { VAR_GENERIC = 0, VAR_GAUSS_UNIT = 1, VAR_TAPE = 2, VAR_GAMMA = 3, VAR_MIX = 4 };
 
 // ---- argument block ------------------------------------------------------------
 template <int D>
@@ -106,6 +108,47 @@ struct StepArgs {
     double* dump_r;
     float* dump_z;
 };
+
+// VAR_MIX: the tables of a glabc_mixture compacted to the D coordinates in use (about 1 KB at D = 4), by value behind the
+// StepArgs.  The density loop indexes them with the wave-uniform mode counter, so they arrive by scalar loads.
+template <int D>
+struct MixArgs {
+    int32_t n_modes;
+    int32_t reserved;
+    double c0;
+    double log_weight[GLABC_MAX_MODES], cum_weight[GLABC_MAX_MODES], sum_log_scale[GLABC_MAX_MODES];
+    double loc[GLABC_MAX_MODES][D], scale[GLABC_MAX_MODES][D], inv_scale[GLABC_MAX_MODES][D];
+};
+
+template <int D, int YD = D>
+struct MixStepArgs : StepArgs<D, YD> {
+    MixArgs<D> mix;
+};
+
+// the argument block of a kernel variant
+template <int D, int YD, int VAR>
+struct KernelArgs {
+    using type = StepArgs<D, YD>;
+};
+template <int D, int YD>
+struct KernelArgs<D, YD, VAR_MIX> {
+    using type = MixStepArgs<D, YD>;
+};
+
+// The tables of the kernel's argument `a`, where they lie in the kernel-argument segment.  Read from there, and not from the
+// by-value copy of the argument, a run-time mode index is an offset of a scalar load; indexing the copy made the compiler keep
+// the whole block in scratch in the larger instantiations.  The parameter type is the guard: only a kernel whose argument block
+// is a MixStepArgs (sampler_kernel<.., VAR_MIX, ..>, init_weights_mix_kernel) has one to hand over, and chain_step passes it on
+// under that type (KernelArgs), so a kernel that takes a plain StepArgs -- team, lane-group, run-time compiled -- cannot reach
+// this function.  The block must be the kernel's FIRST argument, passed as it arrived.
+template <int D, int YD>
+GLABC_DEV const MixArgs<D>& mix_of(const MixStepArgs<D, YD>&)
+{
+    constexpr unsigned long OFF = (sizeof(StepArgs<D, YD>) + 7ul) & ~7ul;
+    static_assert(sizeof(MixStepArgs<D, YD>) == OFF + sizeof(MixArgs<D>), "MixStepArgs = StepArgs, then the tables");
+    const char* base = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(const MixArgs<D>*)(base + OFF);
+}
 
 // ---- torch.sum association over a contiguous float32 row (GLMCMC.py:82) ---------
 // Probed on the reference's torch build (DESIGN.md "row-sum order"): n < 8 -> four
@@ -326,6 +369,112 @@ GLABC_DEV void dist_gamma_forward(const DistArgs<D>& g, uint32_t c0, uint32_t c1
         }
     }
     lq = (float)aten_rowsum_f64<D>(t);
+}
+
+// ---- GaussianMixture, distribution.py:206-293, in double (the specification is in include/glabc.h) ------------------------
+// one mode's term t_k of log_prob at z: k is wave-uniform (a loop counter), so the mode's parameters are scalar loads
+template <int D>
+GLABC_DEV double mix_mode_term(const MixArgs<D>& m, int k, const double (&z)[D])
+{
+    double t[D];
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+        const double e = (z[q] - m.loc[k][q]) * m.inv_scale[k][q];
+        t[q] = e * e;
+    }
+    return glabc_mix_term(m.c0 + m.log_weight[k], aten_rowsum_f64<D>(t), m.sum_log_scale[k]);
+}
+
+// logsumexp over the n_modes terms: max, then the exponentials summed in torch.sum's float64 order for a row of n_modes
+// (aten_rowsum_f64 for a run-time length <= 8: fewer than four terms in sequence; else four partials, terms 4.. into a tail
+// when n_modes < 8 and onto the partials when n_modes == 8; tail first, then the partials in order).  Two passes that each
+// recompute t_k (4 D operations) instead of one that keeps eight doubles per evaluation.
+template <int D>
+GLABC_DEV double mix_log_prob(const MixArgs<D>& m, const double (&z)[D])
+{
+    const int K = m.n_modes;
+    double mx = -__builtin_inf();
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+        const double t = mix_mode_term<D>(m, k, z);
+        mx = t > mx ? t : mx;
+    }
+    if (mx == -__builtin_inf() || mx == __builtin_inf()) mx = 0.0;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, tail = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+        const double e = glabc_exp(mix_mode_term<D>(m, k, z) - mx);
+        if (k < 4) {
+            a0 = k == 0 ? e : a0;
+            a1 = k == 1 ? e : a1;
+            a2 = k == 2 ? e : a2;
+            a3 = k == 3 ? e : a3;
+        } else if (K == 8) {
+            a0 = k == 4 ? a0 + e : a0;
+            a1 = k == 5 ? a1 + e : a1;
+            a2 = k == 6 ? a2 + e : a2;
+            a3 = k == 7 ? a3 + e : a3;
+        } else {
+            tail = tail + e;
+        }
+    }
+    double s;
+    if (K < 4) {
+        s = a0;
+        if (K > 1) s = s + a1;
+        if (K > 2) s = s + a2;
+    } else {
+        s = (((tail + a0) + a1) + a2) + a3;
+    }
+    return mx + glabc_log(s);
+}
+
+// GaussianMixture.log_prob at a float32 state: (float) log_prob((double) theta)
+template <int D>
+GLABC_DEV float dist_mix_log_prob(const MixArgs<D>& m, const float (&z)[D])
+{
+    double zd[D];
+#pragma unroll
+    for (int q = 0; q < D; ++q) zd[q] = (double)z[q];
+    return (float)mix_log_prob<D>(m, zd);
+}
+
+// the drawn mode is lane-varying: its row of scale / loc is picked with a select chain over the wave-uniform k (a private
+// array indexed by the mode would go to scratch), then z = eps * scale + loc in double, two roundings
+template <int D>
+GLABC_DEV void mix_draw(const MixArgs<D>& m, double u, const float (&eps)[D], double (&z)[D])
+{
+    double sc[D], lc[D];
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+        sc[q] = m.scale[0][q];
+        lc[q] = m.loc[0][q];
+    }
+#pragma unroll 1
+    for (int k = 1; k < m.n_modes; ++k) {
+        const bool up = !(u < m.cum_weight[k - 1]);      // the first k with u < cum_weight[k], else n_modes - 1
+#pragma unroll
+        for (int q = 0; q < D; ++q) {
+            sc[q] = up ? m.scale[k][q] : sc[q];
+            lc[q] = up ? m.loc[k][q] : lc[q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < D; ++q) z[q] = (double)eps[q] * sc[q] + lc[q];
+}
+
+// GaussianMixture.forward (distribution.py:242-268) for candidate j of (chain, step) from its proposal normals eps:
+// theta' = (float) z, log q' = (float) log_prob(z) of the DOUBLE variate z (include/glabc.h)
+template <int D>
+GLABC_DEV void dist_mix_forward(const MixArgs<D>& m, uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t step, int j,
+                                const float (&eps)[D], float (&th)[D], float& lq)
+{
+    const glabc_u32x4 w = glabc_philox4x32_10(c0, c1, step, GLABC_SLOT_MIX + (uint32_t)j, k0, k1);
+    double z[D];
+    mix_draw<D>(m, glabc_uniform_f64(w.v[0], w.v[1]), eps, z);
+#pragma unroll
+    for (int q = 0; q < D; ++q) th[q] = (float)z[q];
+    lq = (float)mix_log_prob<D>(m, z);
 }
 
 template <int D, bool KNOWN_GAUSS_UNIT = false, bool GAMMA_OK = false>
@@ -680,13 +829,15 @@ GLABC_DEV void refresh_cache(const StepArgs<D, YD>& a, Chain<D, YD>& c)
 //   MH          : log(u) < ((prior'+K') - prior) - K                       GLMCMC.py:96-99
 //                 log(u) < ((((prior'+K') + q) - q') - prior) - K          GlobalMCMC.py:44-47
 template <int ALGO, int D, int YD, int N, int L, int VAR>
-GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t step, int sub, Chain<D, YD>& c, int64_t tape_pos)
+GLABC_DEV bool chain_step(const typename KernelArgs<D, YD, VAR>::type& a, const Rng& rng, uint32_t step, int sub, Chain<D, YD>& c, int64_t tape_pos)
 {
     constexpr bool GU = (VAR == VAR_GAUSS_UNIT);
     constexpr bool TAPE = (VAR == VAR_TAPE);
     constexpr bool GM = (VAR == VAR_GAMMA);
+    constexpr bool MX = (VAR == VAR_MIX);
     static_assert(!TAPE || L == 1, "tape replay runs one lane per chain");
     static_assert(!GM || L == 1, "the Gamma variant runs one lane per chain");
+    static_assert(!MX || L == 1, "the mixture variant runs one lane per chain");
     constexpr int NL = (N + L - 1) / L;            // candidate slots per lane
     constexpr int HEAD = L - 1;                    // the lane with the fewest candidates draws the step head
     // When N is not a multiple of L the last slot of lane L-1 holds no candidate: the step head
@@ -731,6 +882,30 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
             for (int q = 0; q < 4; ++q) hw[q] = 0u;
         }
         take_head();
+    }
+
+    // ---- a GaussianMixture's N candidates and their log q: drawn in a loop of their own, ahead of the unrolled candidate
+    // code, and staged in LDS (each lane reads back only what it wrote: no barrier).  The float64 density is then compiled
+    // once instead of N times, and its temporaries are dead before the N candidates' registers fill.  A candidate's proposal
+    // normals are words 0..D-1 of its first block (D <= 4).
+    [[maybe_unused]] float* mix_stage = nullptr;
+    if constexpr (MX) {
+        static_assert(D <= 4, "the mixture variant is instantiated up to theta_dim 4");
+        __shared__ float mix_lds[N * (D + 1) * 64];
+        mix_stage = mix_lds + (threadIdx.x & 63u);
+#pragma unroll 1
+        for (int j = 0; j < N; ++j) {
+            const glabc_u32x4 o = glabc_philox4x32_10(rng.c0, rng.c1, step, (uint32_t)(1 + j * SPP), rng.k0, rng.k1);
+            float nj[4], ej[D], tm[D], lqm;
+            glabc_normal_pair(o.v[0], o.v[1], &nj[0], &nj[1]);
+            if constexpr (D > 2) glabc_normal_pair(o.v[2], o.v[3], &nj[2], &nj[3]);
+#pragma unroll
+            for (int q = 0; q < D; ++q) ej[q] = nj[q];
+            dist_mix_forward<D>(mix_of(a), rng.c0, rng.c1, rng.k0, rng.k1, step, j, ej, tm, lqm);
+#pragma unroll
+            for (int q = 0; q < D; ++q) mix_stage[(j * (D + 1) + q) * 64] = tm[q];
+            mix_stage[(j * (D + 1) + D) * 64] = lqm;
+        }
     }
 
     // ---- this lane's candidates ----
@@ -795,11 +970,24 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
                 for (int q = 0; q < D; ++q) th[r][q] = loc ? th[r][q] : tg[q];
             }
         }
+        // a GaussianMixture importance / global proposal: the candidate and forward()'s log q from the candidate's own
+        // proposal normals and the chain's mixture slot; the lanes on the local branch keep candidate 0 as built above
+        float lq_mix = 0.0f;
+        if constexpr (MX) {
+            lq_mix = mix_stage[(r * (D + 1) + D) * 64];
+#pragma unroll
+            for (int q = 0; q < D; ++q) th[r][q] = loc ? th[r][q] : mix_stage[(r * (D + 1) + q) * 64];
+        }
         // log q of the proposal under the global distribution: from its noise (forward(), GLMCMC.py:66) for an iSIR
         // candidate; for GLMCMC's local move q(theta') itself, so that lw / wl of slot 0 are the log-weight and weight
         // the proposed state will carry if it is accepted (what GLMCMC.py:60-64 computes at the next global step)
         float lq;
-        if constexpr (ALGO == ALGO_GLMCMC && GU) {
+        if constexpr (MX) {
+            lq = lq_mix;                                                      // unused by GlobalMCMC's local move
+            if constexpr (ALGO == ALGO_GLMCMC) {
+                if (loc) lq = dist_mix_log_prob<D>(mix_of(a), th[r]);
+            }
+        } else if constexpr (ALGO == ALGO_GLMCMC && GU) {
             float v[D];                                                       // both are c0 - sum 0.5 v^2 in the unit variant
 #pragma unroll
             for (int q = 0; q < D; ++q) v[q] = loc ? (th[r][q] - a.global.p0[q]) : e[q];
@@ -903,14 +1091,24 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
 #pragma unroll
         for (int r = 1; r < NL; ++r) {
             if (slot == r) {                      // (measured: these small masked blocks beat per-value selects)
+                if constexpr (!MX) {
 #pragma unroll
-                for (int q = 0; q < D; ++q) nt[q] = th[r][q];
+                    for (int q = 0; q < D; ++q) nt[q] = th[r][q];
+                }
 #pragma unroll
                 for (int q = 0; q < YD; ++q) ny[q] = yy[r][q];
                 nlw = lw[r];
                 npr = pr[r];
                 nkk = kk[r];
                 if (CARRY_W) nw = wl[r];
+            }
+        }
+        if constexpr (MX) {
+            // candidates 1.. are global candidates, still in the staging area: read the winner's back from there (the lane's own
+            // slot index) instead of keeping all N theta' in registers; candidate 0, which may be the local move, is nt already
+            if (slot > 0) {
+#pragma unroll
+                for (int q = 0; q < D; ++q) nt[q] = mix_stage[(slot * (D + 1) + q) * 64];
             }
         }
 #pragma unroll
@@ -928,7 +1126,10 @@ GLABC_DEV bool chain_step(const StepArgs<D, YD>& a, const Rng& rng, uint32_t ste
             for (int q = 0; q < YD; ++q) c.y[q] = ny[q];
             c.prior = npr;
             c.kern = nkk;
-            c.q = dist_log_prob<D, GU, GM>(a.global, c.theta);
+            if constexpr (MX)
+                c.q = dist_mix_log_prob<D>(mix_of(a), c.theta);
+            else
+                c.q = dist_log_prob<D, GU, GM>(a.global, c.theta);
             if (ALGO == ALGO_GLMCMC) {
                 c.lw_cur = nlw;
                 c.w_cur = CARRY_W ? nw : isir_weight(nlw);                    // the specified weight, never the fast one

@@ -1,0 +1,41 @@
+// glabc_mix.h -- host side of the GaussianMixture variant (VAR_MIX, glabc_device.h): the per-dimension launchers of
+// glabc_mix_dim.hip and the packing of a glabc_mixture into the kernels' argument block.  Never handed to hiprtc.
+#pragma once
+
+#include <cstring>
+
+#include "glabc_sampler.h"
+
+namespace glabc {
+
+// the mixture's tables compacted to the D coordinates in use
+template <int D>
+inline MixArgs<D> pack_mixture(const glabc_mixture* g)
+{
+    MixArgs<D> o;
+    std::memset(&o, 0, sizeof o);
+    o.n_modes = g->n_modes;
+    o.c0 = g->c0;
+    for (int k = 0; k < GLABC_MAX_MODES; ++k) {
+        o.log_weight[k] = g->log_weight[k];
+        o.cum_weight[k] = g->cum_weight[k];
+        o.sum_log_scale[k] = g->sum_log_scale[k];
+        for (int q = 0; q < D; ++q) {
+            o.loc[k][q] = g->loc[k][q];
+            o.scale[k][q] = g->scale[k][q];
+            o.inv_scale[k][q] = g->inv_scale[k][q];
+        }
+    }
+    return o;
+}
+
+// GLMCMC (n_batch 1..GLABC_MAX_BATCH) or GlobalMCMC at one lane per chain, default schedule; defined in glabc_mix_dim.hip
+// (one TU per theta_dim and for the g-and-k shape).  Returns a glabc_status.
+template <int D, int YD>
+int launch_mix_dim(int algo, int n_batch, const MixStepArgs<D, YD>& a, hipStream_t stream);
+
+// GLMCMC.py:52-55 with the mixture as the importance proposal
+template <int D, int YD>
+int launch_init_weights_mix_dim(const MixStepArgs<D, YD>& a, hipStream_t stream);
+
+}  // namespace glabc

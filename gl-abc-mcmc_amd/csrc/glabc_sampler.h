@@ -21,7 +21,7 @@ constexpr int BLOCK = 64;      // one wavefront per workgroup: 65 536 chains x L
 // to a 2 % slower kernel -- 224 instead of 219 VGPRs, 40 instead of 43 scalar loads -- measured back to back on one box.  The
 // run-time compiled form of glabc_rtc.hip therefore instantiates this very template.)
 template <int ALGO, int D, int YD, int N, int L, int VAR, int SCHED>
-__global__ void __launch_bounds__(BLOCK) sampler_kernel(const StepArgs<D, YD> a)
+__global__ void __launch_bounds__(BLOCK) sampler_kernel(const typename KernelArgs<D, YD, VAR>::type a)
 {
     const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const int64_t chain = tid / L;
@@ -41,6 +41,7 @@ __global__ void __launch_bounds__(BLOCK) sampler_kernel(const StepArgs<D, YD> a)
     c.n_moves = a.n_moves ? a.n_moves[i] : 0u;
     c.gf = a.gf_chain ? a.gf_chain[i] : a.gf;
     refresh_cache<D, YD, VAR == VAR_GAMMA>(a, c);
+    if constexpr (VAR == VAR_MIX) c.q = dist_mix_log_prob<D>(mix_of<D, YD>(a), c.theta);      // the placeholder's q is never read
     c.lw_cur = (c.flags & GLABC_FLAG_LOCAL) ? (c.prior + c.kern) - c.q : c.log_w;          // GLMCMC.py:60-64
     {
         const float v = glabc_expf(c.lw_cur);

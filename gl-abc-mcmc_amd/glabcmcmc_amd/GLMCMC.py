@@ -19,7 +19,9 @@ Dispatch (``path``): a Model and proposals that describe themselves (``descripto
 shape; batch_size <= 4096) run in the fused kernels (above 16 proposals lane groups of a wavefront share a chain).  A
 ``distribution.Gamma`` prior or importance proposal is fused on the |theta| + noise Model up to theta_dim 4, on g-and-k
 (``GK_set(prior=...)``) and on a ``CompiledModel`` (its programs are then compiled with the Gamma kernels); a Gamma local increment
-is a callback and runs split-phase.  A
+is a callback and runs split-phase.  A ``distribution.GaussianMixture`` importance proposal (up to 8 modes) is fused on the
+|theta| + noise Model up to theta_dim 4 and on g-and-k for batch_size <= 16 with a DiagGaussian / Uniform prior: ``"auto"`` then draws
+it from the kernel's Philox stream instead of torch's generator (the same law); ``path="generic"`` keeps the callback.  A
 ``compiled.CompiledModel`` (a user's simulator compiled into those kernels at run time) runs fused as well: up to 16 proposals in a register kernel
 compiled for the batch size, 17..4096 in the lane-group kernel compiled once per Model -- except that ``"auto"`` keeps one with a
 user prior on the split-phase path above 16 proposals (only that path redraws the 7 log(1e-10) prior sentinel), and falls back
@@ -48,7 +50,8 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
         raise ValueError("fast_math is a variant of the fused kernel (glabc_run.math_mode = GLABC_MATH_FAST)")
     # fast_math names the fused kernel's variant: "auto" takes the fused path for it unconditionally
     fused = path == "fused" or (path == "auto" and (fast_math or generic.fused_supported(ABCset, (Local_Proposal, Importance_Proposal),
-                                                                                         batch_size, _capi.MAX_BATCH_WIDE, gamma_ok=True)))
+                                                                                         batch_size, _capi.MAX_BATCH_WIDE, gamma_ok=True,
+                                                                                         mixture_ok=True)))
     rtc = None
     if fused and path == "auto" and not fast_math and int(batch_size) > _capi.MAX_BATCH and \
             getattr(generic.try_descriptor(ABCset), "sim_kind", None) == _capi.SIM_USER:
@@ -69,6 +72,9 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
     model = engine.model_descriptor(ABCset)
     local = Local_Proposal.descriptor()
     imp = Importance_Proposal.descriptor()
+    mix = isinstance(imp, _capi.Mixture)                           # a GaussianMixture: the kernels' mixture variant (include/glabc.h)
+    if mix and (fast_math or model.sim_kind == _capi.SIM_USER):
+        raise ValueError("a GaussianMixture importance proposal runs fused without fast_math and on the built-in Models only")
     dev, chains, single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
     hist = _host.allocate_history(num_ite, chains, record_history)
     mirror = _host.HostMirror(hist) if _host.HostMirror.wanted(hist, single, return_device) else None   # rows leave for the host while the kernels run
@@ -77,7 +83,7 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
             rtc = generic.rtc_program(ABCset, model, Importance_Proposal, _capi.ALGO_GLMCMC, batch_size)
     else:
         engine.init_weights(model, imp, chains)                    # GLMCMC.py:52-55
-    engine.run_steps("glabc_glmcmc_steps", model, local, imp, chains, num_ite - 1, 1, engine.draw_seed(seed),
+    engine.run_steps("glabc_glmcmc_mix_steps" if mix else "glabc_glmcmc_steps", model, local, imp, chains, num_ite - 1, 1, engine.draw_seed(seed),
                      global_frequency, batch_size, history=None if hist is None else hist[1:], moments=stats,
                      steps_per_launch=steps_per_launch, rtc_program=rtc, mirror=mirror,
                      math_mode=_capi.MATH_FAST if fast_math else _capi.MATH_EXACT)

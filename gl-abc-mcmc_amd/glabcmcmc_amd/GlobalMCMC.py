@@ -1,7 +1,8 @@
 """GlobalMCMC -- independence-MH global move + random-walk MH local move
 (reference: GlobalMCMC.py:6-98).  Same positional signature; the loop body
 (GlobalMCMC.py:37-68) is the fused gfx950 kernel behind ``glabc_globalmcmc_steps``.
-Shapes, return value, keyword-only extras and the fused / generic dispatch (``path``) as in ``GLMCMC``."""
+Shapes, return value, keyword-only extras and the fused / generic dispatch (``path``) as in ``GLMCMC``, a
+``distribution.GaussianMixture`` global proposal included."""
 from . import _capi, _host, engine, generic
 
 
@@ -15,7 +16,8 @@ def GlobalMCMC(ABCset, num_ite, Initial_theta, Initial_y,
         Local_Proposal = Global_Proposal
     if path not in ("auto", "fused", "generic"):
         raise ValueError("path must be 'auto', 'fused' or 'generic'")
-    if path == "generic" or (path == "auto" and not generic.fused_supported(ABCset, (Local_Proposal, Global_Proposal), 1, gamma_ok=True)):
+    if path == "generic" or (path == "auto" and not generic.fused_supported(ABCset, (Local_Proposal, Global_Proposal), 1, gamma_ok=True,
+                                                                            mixture_ok=True)):
         return generic.run(_capi.ALGO_GLOBALMCMC, ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Global_Proposal,
                            filelocation, global_frequency, 1, "global", seed=seed, device=device, chain0=chain0,
                            record_history=record_history, stats=stats, return_device=return_device, verbose=verbose,
@@ -25,11 +27,14 @@ def GlobalMCMC(ABCset, num_ite, Initial_theta, Initial_y,
     model = engine.model_descriptor(ABCset)
     local = Local_Proposal.descriptor()
     glob = Global_Proposal.descriptor()
+    mix = isinstance(glob, _capi.Mixture)                          # a GaussianMixture: the kernels' mixture variant (include/glabc.h)
+    if mix and model.sim_kind == _capi.SIM_USER:
+        raise ValueError("a GaussianMixture global proposal runs fused on the built-in Models only")
     dev, chains, single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
     hist = _host.allocate_history(num_ite, chains, record_history)
     mirror = _host.HostMirror(hist) if _host.HostMirror.wanted(hist, single, return_device) else None   # rows leave for the host while the kernels run
     rtc = generic.rtc_program(ABCset, model, Global_Proposal, _capi.ALGO_GLOBALMCMC) if model.sim_kind == _capi.SIM_USER else None   # CompiledModel
-    engine.run_steps("glabc_globalmcmc_steps", model, local, glob, chains, num_ite - 1, 1, engine.draw_seed(seed),
+    engine.run_steps("glabc_globalmcmc_mix_steps" if mix else "glabc_globalmcmc_steps", model, local, glob, chains, num_ite - 1, 1, engine.draw_seed(seed),
                      global_frequency, 1, history=None if hist is None else hist[1:], moments=stats,
                      steps_per_launch=steps_per_launch, rtc_program=rtc, mirror=mirror)
     if state_out is not None:

@@ -10,6 +10,7 @@ import ctypes as C
 import os
 
 MAX_DIM = 8
+MAX_MODES = 8             # GLABC_MAX_MODES: modes of a glabc_mixture
 MAX_BATCH = 16            # register kernels (and every sampler but GLMCMC)
 MAX_BATCH_WIDE = 4096      # glabc_glmcmc_steps: lane groups of a wavefront share a chain's proposals
 
@@ -159,6 +160,21 @@ class GammaDesc(C.Structure):
     ]
 
 
+class Mixture(C.Structure):
+    """struct glabc_mixture"""
+    _fields_ = [
+        ("n_modes", C.c_int32),
+        ("dim", C.c_int32),
+        ("loc", (C.c_double * MAX_DIM) * MAX_MODES),
+        ("scale", (C.c_double * MAX_DIM) * MAX_MODES),
+        ("inv_scale", (C.c_double * MAX_DIM) * MAX_MODES),
+        ("log_weight", C.c_double * MAX_MODES),
+        ("cum_weight", C.c_double * MAX_MODES),
+        ("sum_log_scale", C.c_double * MAX_MODES),
+        ("c0", C.c_double),
+    ]
+
+
 class Moments(C.Structure):
     """struct glabc_moments"""
     _fields_ = [
@@ -288,6 +304,11 @@ ENTRY_POINTS = {
     "glabc_dist_forward": (C.c_int, [_P(Dist), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_gamma_log_prob": (C.c_int, [_P(GammaDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_gamma_forward": (C.c_int, [_P(GammaDesc), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glabc_mixture_log_prob": (C.c_int, [_P(Mixture), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "glabc_mixture_forward": (C.c_int, [_P(Mixture), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glabc_init_weights_mix": (C.c_int, [_P(Model), _P(Mixture), _P(Chains), C.c_void_p]),
+    "glabc_glmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
+    "glabc_globalmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_model_prior_log_prob": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_model_discrepancy": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_model_log_kernel": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

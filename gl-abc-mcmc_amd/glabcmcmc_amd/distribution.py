@@ -61,6 +61,14 @@ def _launch_simulate(desc, theta, eps):
     return y
 
 
+def generic_descriptor(dist):
+    """dist.descriptor(), or None where the struct cannot hold the distribution"""
+    try:
+        return dist.descriptor()
+    except ValueError:
+        return None
+
+
 class BaseDistribution:
     """distribution.py:7-48"""
 
@@ -261,9 +269,12 @@ class DiagGaussian(BaseDistribution):
 
 
 class GaussianMixture(BaseDistribution):
-    """Mixture of diagonal Gaussians (distribution.py:206-293); API surface only, torch ops."""
+    """Mixture of diagonal Gaussians (distribution.py:206-293); float64.  ``descriptor()`` is the ``glabc_mixture`` struct the
+    fused GLMCMC / GlobalMCMC kernels take as importance / global proposal; on CUDA tensors ``log_prob`` and, with a CUDA
+    ``device``, ``forward`` run the gfx950 kernels (include/glabc.h gives their arithmetic).  On the CPU: torch ops, as the
+    reference."""
 
-    def __init__(self, n_modes, dim, loc=None, scale=None, weights=None):
+    def __init__(self, n_modes, dim, loc=None, scale=None, weights=None, *, device=None, seed=None):
         super().__init__()
         self.n_modes = n_modes
         self.dim = dim
@@ -277,6 +288,37 @@ class GaussianMixture(BaseDistribution):
         self.loc = torch.nn.Parameter(torch.tensor(1.0 * loc))
         self.log_scale = torch.nn.Parameter(torch.tensor(np.log(1.0 * scale)))
         self.weight_scores = torch.nn.Parameter(torch.tensor(np.log(1.0 * weights)))
+        # device / seed are additions, as for Gamma: with a CUDA device forward() draws on the GPU (glabc_mixture_forward on the
+        # Philox stream of `seed`, a fresh block of rows per call); without, the reference's torch draw
+        self.device = None if device is None else torch.device(device)
+        self.seed = seed
+        self._rows_drawn = 0
+
+    def descriptor(self):
+        """glabc_mixture (include/glabc.h): the constants formed here in float64 exactly as the header lists them"""
+        K, d = int(self.n_modes), int(self.dim)
+        if not 1 <= K <= _capi.MAX_MODES:
+            raise ValueError("GaussianMixture descriptor: 1..%d modes, got %d" % (_capi.MAX_MODES, K))
+        if not 1 <= d <= _capi.MAX_DIM:
+            raise ValueError("GaussianMixture dim %d > GLABC_MAX_DIM" % d)
+        with torch.no_grad():
+            log_scale = self.log_scale.detach().to(torch.float64).cpu().reshape(1, K, d)
+            scores = self.weight_scores.detach().to(torch.float64).cpu().reshape(1, K)
+            loc = self.loc.detach().to(torch.float64).cpu().reshape(1, K, d)[0].numpy()
+            scale = torch.exp(log_scale)[0].numpy()
+            inv_scale = 1.0 / scale
+            weights = torch.softmax(scores, 1)
+            log_weight = torch.log(weights)[0].numpy()
+            cum_weight = np.cumsum(weights[0].numpy())
+            sum_log_scale = torch.sum(log_scale, 2)[0].numpy()
+        m = _capi.Mixture()
+        m.n_modes, m.dim = K, d
+        for k in range(K):
+            for q in range(d):
+                m.loc[k][q], m.scale[k][q], m.inv_scale[k][q] = float(loc[k, q]), float(scale[k, q]), float(inv_scale[k, q])
+            m.log_weight[k], m.cum_weight[k], m.sum_log_scale[k] = float(log_weight[k]), float(cum_weight[k]), float(sum_log_scale[k])
+        m.c0 = float(-0.5 * d * np.log(2 * np.pi))
+        return m
 
     def _mode_log_p(self, z):
         weights = torch.softmax(self.weight_scores, 1)
@@ -284,7 +326,27 @@ class GaussianMixture(BaseDistribution):
         return (-0.5 * self.dim * np.log(2 * np.pi) + torch.log(weights)
                 - 0.5 * torch.sum(torch.pow(eps, 2), 2) - torch.sum(self.log_scale, 2))
 
-    def forward(self, num_samples=1):
+    def forward(self, num_samples=1, seed=None, row0=None):
+        # no `device` argument: the split-phase path offers one to a callback proposal (generic.ProposalCallbacks) and a mixture
+        # built without a device keeps drawing from torch's generator there, as before
+        dev = self.device
+        if dev is not None and dev.type == "cuda":
+            desc = self.descriptor()
+            if seed is None:
+                if self.seed is None:
+                    self.seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+                seed = self.seed
+            if row0 is None:
+                row0 = self._rows_drawn
+                self._rows_drawn += int(num_samples)
+            z = torch.empty(num_samples, desc.dim, dtype=torch.float64, device=dev)
+            log_p = torch.empty(num_samples, dtype=torch.float64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            with torch.cuda.device(dev):
+                _capi.check(_capi.lib().glabc_mixture_forward(C.byref(desc), int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                              int(row0), z.data_ptr(), log_p.data_ptr(), C.c_void_p(stream)),
+                            "GaussianMixture.forward")
+            return z, log_p
         weights = torch.softmax(self.weight_scores, 1)
         mode = torch.multinomial(weights[0, :], num_samples, replacement=True)
         mode_1h = torch.nn.functional.one_hot(mode, self.n_modes)[..., None]
@@ -295,6 +357,19 @@ class GaussianMixture(BaseDistribution):
         return z, torch.logsumexp(self._mode_log_p(z), 1)
 
     def log_prob(self, z):
+        # the kernel where the struct holds the mixture and no gradient is asked for; else torch ops, as before the kernel existed
+        # (a mixture of more than 8 modes moved to the device, a log_prob that autograd follows)
+        desc = generic_descriptor(self) if z.is_cuda and not (torch.is_grad_enabled() and z.requires_grad) else None
+        if desc is not None:
+            zz = z.detach().to(torch.float64).reshape(z.shape[0], -1).contiguous()
+            if zz.shape[1] != desc.dim:
+                raise ValueError("GaussianMixture.log_prob: %d columns for a mixture of dimension %d" % (zz.shape[1], desc.dim))
+            out = torch.empty(zz.shape[0], dtype=torch.float64, device=z.device)
+            stream = torch.cuda.current_stream(z.device).cuda_stream
+            with torch.cuda.device(z.device):
+                _capi.check(_capi.lib().glabc_mixture_log_prob(C.byref(desc), zz.data_ptr(), zz.shape[0], out.data_ptr(),
+                                                               C.c_void_p(stream)), "GaussianMixture.log_prob")
+            return out
         if self.dim == 1 and z.dim() == 1:
             z = z[:, None]
         return torch.logsumexp(self._mode_log_p(z), 1)

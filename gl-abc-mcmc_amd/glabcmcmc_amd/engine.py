@@ -135,7 +135,8 @@ def run_steps(entry, model_desc, local_desc, global_desc, chains, n_steps, step0
               history=None, moments=None, steps_per_launch=None, lanes_per_chain=0, debug_flags=0, gf_per_chain=None,
               rtc_program=None, math_mode=0, dump_draws=None, mirror=None):
     """Advance `chains` by n_steps iterations with the C-ABI entry point `entry`
-    ('glabc_glmcmc_steps' / 'glabc_globalmcmc_steps'), K iterations per launch.
+    ('glabc_glmcmc_steps' / 'glabc_globalmcmc_steps', or their '_mix_steps' twins when global_desc is a _capi.Mixture), K
+    iterations per launch.
 
     history: None or float32 tensor [n_steps][d][C] on the chains' device.
     lanes_per_chain: 0 = let the library choose from the chain count; 1 / 2 / 4 force the
@@ -244,12 +245,13 @@ def run_glmala_steps(model_desc, importance_desc, mala, chains, n_steps, step0, 
 
 
 def init_weights(model_desc, importance_desc, chains):
+    """GLMCMC.py:52-55; a _capi.Mixture importance proposal goes to the mixture entry point"""
     lib = _capi.lib()
+    entry = "glabc_init_weights_mix" if isinstance(importance_desc, _capi.Mixture) else "glabc_init_weights"
     cs = chains.struct()
     stream = torch.cuda.current_stream(chains.device).cuda_stream
     with torch.cuda.device(chains.device):
-        _capi.check(lib.glabc_init_weights(C.byref(model_desc), C.byref(importance_desc), C.byref(cs),
-                                           C.c_void_p(stream)), "glabc_init_weights")
+        _capi.check(getattr(lib, entry)(C.byref(model_desc), C.byref(importance_desc), C.byref(cs), C.c_void_p(stream)), entry)
 
 
 def model_descriptor(abc_set):

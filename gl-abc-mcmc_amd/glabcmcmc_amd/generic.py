@@ -73,17 +73,24 @@ def rtc_program(ABCset, model_desc, proposal, algo, batch_size=1):
     return ABCset.program(algo, batch_size)
 
 
-def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, gamma_ok=False):
+def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, gamma_ok=False, mixture_ok=False):
     """Can the fused kernels (glabc_glmcmc_steps / glabc_globalmcmc_steps / glabc_glmala_steps) run this configuration?
     gamma_ok: the entry point knows GLABC_DIST_GAMMA as the LAST proposal (importance / global) and as the Model's prior --
     GLMCMC and GlobalMCMC on the |theta| + noise Model up to theta_dim 4, on g-and-k and on a compiled.CompiledModel, whose
-    programs are then compiled with GLABC_RTC_GAMMA (include/glabc.h)."""
+    programs are then compiled with GLABC_RTC_GAMMA (include/glabc.h).
+    mixture_ok: the caller has the mixture entry points (glabc_glmcmc_mix_steps / glabc_globalmcmc_mix_steps): a
+    distribution.GaussianMixture (a _capi.Mixture descriptor) as the LAST proposal, on the |theta| + noise Model up to theta_dim 4
+    and on g-and-k, batch sizes up to GLABC_MAX_BATCH, no Gamma prior; anywhere else a mixture stays a callback."""
     m = try_descriptor(ABCset)
     if m is None or not isinstance(m, _capi.Model):
         return False
     gamma = m.prior.kind == _capi.DIST_GAMMA
     for i, p in enumerate(proposals):
         d = try_descriptor(p)
+        if isinstance(d, _capi.Mixture):
+            return bool(mixture_ok and i == len(proposals) - 1 and i > 0 and d.dim == m.theta_dim and not gamma and
+                        ((m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4) or m.sim_kind == _capi.SIM_GK) and
+                        (batch_size is None or 1 <= int(batch_size) <= _capi.MAX_BATCH))
         if d is None or not isinstance(d, _capi.Dist) or d.dim != m.theta_dim:
             return False
         if d.kind == _capi.DIST_GAMMA:

@@ -560,6 +560,63 @@ int glabc_gamma_log_prob(const glabc_gamma* dist, const double* z, int64_t n, do
 int glabc_gamma_forward(const glabc_gamma* dist, int64_t n, uint64_t seed, int64_t row0, double* z_out, double* log_p_out,
                         void* stream);
 
+/* ---- GaussianMixture, distribution.py:206-293: a mixture of diagonal Gaussians as the importance / global proposal ------------
+ * The reference's mixture is float64 end to end (its parameters are float64 tensors); the chains' state is float32 here, so, as
+ * for GLABC_DIST_GAMMA above, everything is computed in double and rounded once to the float32 state.  The constants are
+ * formed on the HOST in float64 (the Python class, with torch / numpy) and cross the ABI as numbers:
+ *   loc[k][q]; scale[k][q] = torch.exp(log_scale); inv_scale[k][q] = 1.0 / scale; log_weight[k] = torch.log(torch.softmax(
+ *   weight_scores, 1)); cum_weight[k] = np.cumsum(softmax weights); sum_log_scale[k] = torch.sum(log_scale, 2);
+ *   c0 = -0.5 * dim * np.log(2 * np.pi).
+ * log_prob(z), z in double (distribution.py:284-291):
+ *   S_k = sum_q ((z_q - loc[k][q]) * inv_scale[k][q])^2     each square one multiplication, the sum in torch.sum's float64 order
+ *   t_k = ((c0 + log_weight[k]) - 0.5 * S_k) - sum_log_scale[k]
+ *   m + glabc_log(sum_k glabc_exp(t_k - m)),  m = max_k t_k, 0 if that is infinite; the sum over k in the same row-sum order
+ * with no contraction into fma anywhere.  ONE DEVIATION from the reference's arithmetic: (z - loc) is MULTIPLIED by the
+ * host-formed reciprocal inv_scale instead of divided by scale -- a float64 division per mode, coordinate and evaluation would
+ * be the most expensive operation of the loop.  The result is therefore not bit-identical to torch's; it stays within
+ * 1e-12 * max(1, |value|) of it (tests/test_mixture_host.py), the bound the Gamma density is held to.
+ * forward inside a sampler, candidate j of (chain, iteration):
+ *   u = glabc_uniform_f64(w0, w1) of the Philox block at counter (chain lo, chain hi, iteration, GLABC_SLOT_MIX + j)
+ *   mode k = the first k with u < cum_weight[k], else n_modes - 1
+ *   eps_q = the candidate's ordinary proposal normals (words 0..dim-1 of its blocks, Box-Muller pairs) promoted to double
+ *   z_q = eps_q * scale[k][q] + loc[k][q] (two roundings), theta'_q = (float) z_q, log q' = (float) log_prob(z) -- the density
+ *   of the DOUBLE variate, as for Gamma.  log_prob of a float32 state is (float) log_prob((double) theta).
+ * Existing draws are untouched (GLABC_STREAM_LAYOUT stays 2).
+ * Where the fused samplers take it (glabc_glmcmc_mix_steps / glabc_globalmcmc_mix_steps / glabc_init_weights_mix): GLABC_SIM_ABS_GAUSS
+ * with theta_dim 1..4 and GLABC_SIM_GK, batch size 1..GLABC_MAX_BATCH, prior and local increment DiagGaussian or Uniform, with
+ * history, moments, global_frequency_per_chain and GLABC_DEBUG_EXACT_INDEX; one lane per chain in the default schedule
+ * (lanes_per_chain 0 or 1).  Refused: theta_dim 5..8 and a Gamma prior (GLABC_ERR_KIND), a tape and GLABC_MATH_FAST
+ * (GLABC_ERR_ARG), n_modes outside 1..GLABC_MAX_MODES (GLABC_ERR_ARG), dim != theta_dim (GLABC_ERR_DIM), a scale or inv_scale
+ * that is not finite and > 0, a non-monotone cum_weight or a last cum_weight outside (0, 1 + 1e-9] (GLABC_ERR_ARG). */
+#define GLABC_MAX_MODES 8
+typedef struct glabc_mixture {
+    int32_t n_modes;               /* 1..GLABC_MAX_MODES */
+    int32_t dim;                   /* 1..GLABC_MAX_DIM */
+    double loc[GLABC_MAX_MODES][GLABC_MAX_DIM];
+    double scale[GLABC_MAX_MODES][GLABC_MAX_DIM];
+    double inv_scale[GLABC_MAX_MODES][GLABC_MAX_DIM];
+    double log_weight[GLABC_MAX_MODES];
+    double cum_weight[GLABC_MAX_MODES];
+    double sum_log_scale[GLABC_MAX_MODES];
+    double c0;
+} glabc_mixture;
+
+/* GaussianMixture.log_prob: z[n][dim] row-major float64, dim 1..8 -> out[n] float64 (mirrors glabc_gamma_log_prob). */
+int glabc_mixture_log_prob(const glabc_mixture* dist, const double* z, int64_t n, double* out, void* stream);
+
+/* GaussianMixture.forward(n) drawn on the device, in the layout of glabc_kde_sample: row r (global id row0 + r) reads
+ * Philox(seed; id lo, id hi, 0, b): the mode uniform from words 0-1 of block 0, the normals from words 2-3 of block 0, then
+ * blocks 1 and up.  z_out[n][dim] row-major float64, log_p_out[n] = log_prob(z_out[r]). */
+int glabc_mixture_forward(const glabc_mixture* dist, int64_t n, uint64_t seed, int64_t row0, double* z_out, double* log_p_out,
+                          void* stream);
+
+/* glabc_init_weights / glabc_glmcmc_steps / glabc_globalmcmc_steps with a mixture as the importance / global proposal. */
+int glabc_init_weights_mix(const glabc_model* model, const glabc_mixture* importance, const glabc_chains* chains, void* stream);
+int glabc_glmcmc_mix_steps(const glabc_model* model, const glabc_dist* local, const glabc_mixture* importance,
+                           const glabc_chains* chains, const glabc_run* run, void* stream);
+int glabc_globalmcmc_mix_steps(const glabc_model* model, const glabc_dist* local, const glabc_mixture* global,
+                               const glabc_chains* chains, const glabc_run* run, void* stream);
+
 /* Model callbacks on n row-major points (Mixture.py:28-45): used by the host
  * mirror's Model class and by the parity tests. */
 int glabc_model_prior_log_prob(const glabc_model* model, const float* theta, int64_t n, float* out, void* stream);

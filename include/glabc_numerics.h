@@ -498,6 +498,17 @@ GLABC_HD double glabc_gamma_draw_candidate(double shape, uint32_t c0, uint32_t c
     return glabc_gamma_draw_at(shape, c0, c1, step, slot0, slot0 + 256u, k0, k1);
 }
 
+/* GaussianMixture as the importance / global proposal INSIDE a sampler iteration (glabc_mixture, include/glabc.h): candidate j of
+ * (chain, iteration) draws its mode from words 0, 1 of the block at counter (chain id lo, hi, iteration, GLABC_SLOT_MIX + j),
+ * j < GLABC_MAX_BATCH.  The region 2^28 .. 2^28 + 16 of the slot word is disjoint from every slot in use: the candidates' own
+ * blocks (below 2^15), GLMALA's gradient noise (below 2^22), Gamma (GLABC_SLOT_GAMMA = 2^29 up to 2^29 + 2^24) and the local
+ * move's redraws (GLABC_SLOT_REDRAW = 2^30 and above). */
+#define GLABC_SLOT_MIX 0x10000000u
+
+/* one mode's term of GaussianMixture.log_prob (distribution.py:285-290) from S = sum_q ((z_q - loc_q) * inv_scale_q)^2 and
+ * cw = c0 + log_weight: (cw - 0.5 S) - sum_log_scale.  Plain IEEE double operations, no contraction. */
+GLABC_HD double glabc_mix_term(double cw, double S, double sum_log_scale) { return (cw - 0.5 * S) - sum_log_scale; }
+
 /* one coordinate of Gamma.log_prob, distribution.py:133-136, float64: log(scipy.stats.gamma.pdf(z, shape, scale = 1/rate)) with
  * -inf where the pdf is 0 (it underflows earlier than a logpdf would -- reproduced);
  *   pdf = exp(xlogy(shape - 1, x) - x - gammaln(shape)) / scale,  x = z / scale,  0 for x < 0 */

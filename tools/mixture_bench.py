@@ -1,0 +1,82 @@
+"""GLMCMC on Mixture_set with a four-mode GaussianMixture importance proposal: whole calls of
+  (a) path="auto"     the fused mixture kernel (glabc_glmcmc_mix_steps),
+  (b) path="generic"  the split-phase path with the mixture as a callback -- what such a call ran before the kernel existed,
+  (c) the fused kernel with a DiagGaussian importance proposal, as context,
+timed with a host clock that ends in a device synchronise.  After a warm-up of each, (a) and (b) alternate in one process;
+the median and the spread (max - min) of the repeats are reported, and (a) beats (b) only if the medians differ by more than
+both spreads.
+
+    python tools/mixture_bench.py [--chains 65536] [--iters 2000] [--batch 5] [--repeats 3] [--out profiles/mixture_bench.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gl-abc-mcmc_amd"))
+import glabcmcmc_amd as g  # noqa: E402
+from glabcmcmc_amd.examples.Mixture import Mixture_set  # noqa: E402
+
+
+def clocked(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", type=int, default=65536)
+    ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--batch", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--warmup-iters", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    model = Mixture_set(0.05)
+    lp = g.DiagGaussian(2, torch.zeros(1, 2), torch.log(torch.tensor([0.35, 0.35])))
+    mix = g.GaussianMixture(4, 2, loc=[[1.5, 1.5], [1.5, -1.5], [-1.5, 1.5], [-1.5, -1.5]], scale=[[0.5, 0.5]] * 4)
+    gauss = g.DiagGaussian(2, torch.tensor([0.0, 0.0]), torch.log(torch.tensor([1.6, 1.6])))
+    gen = torch.Generator().manual_seed(1234)
+    th0 = torch.randn(a.chains, 2, generator=gen)
+    y0 = th0.abs() + (0.05 ** 0.5) * torch.randn(a.chains, 2, generator=gen)
+    kw = dict(seed=20261019, verbose=False, record_history=False)
+
+    def call(ip, path, iters):
+        return lambda: g.GLMCMC(model, iters + 1, th0, y0, lp, None, 0.9, ip, a.batch, path=path, **kw)
+
+    runs = {"fused_mixture": call(mix, "auto", a.iters), "split_phase_mixture": call(mix, "generic", a.iters),
+            "fused_diag_gaussian": call(gauss, "auto", a.iters)}
+    for name, (ip, path) in {"fused_mixture": (mix, "auto"), "split_phase_mixture": (mix, "generic"),
+                             "fused_diag_gaussian": (gauss, "auto")}.items():
+        clocked(call(ip, path, a.warmup_iters))              # warm-up: library load, graphs, caches
+    times = {k: [] for k in runs}
+    for _ in range(a.repeats):                               # (a) and (b) alternate; (c) rides along
+        for name in ("fused_mixture", "split_phase_mixture", "fused_diag_gaussian"):
+            times[name].append(clocked(runs[name]))
+    steps = float(a.chains) * a.iters
+    res = {"workload": "GLMCMC on Mixture_set, theta_dim 2, 4-mode GaussianMixture importance proposal", "chains": a.chains,
+           "iterations": a.iters, "batch_size": a.batch, "repeats": a.repeats, "device": torch.cuda.get_device_name(0)}
+    for name, ts in times.items():
+        res[name] = {"seconds": ts, "median_s": statistics.median(ts), "spread_s": max(ts) - min(ts),
+                     "chain_steps_per_s": steps / statistics.median(ts)}
+    fa, sb = res["fused_mixture"], res["split_phase_mixture"]
+    res["fused_over_split_phase"] = sb["median_s"] / fa["median_s"]
+    res["fused_beats_split_phase_by_more_than_the_spread"] = bool(sb["median_s"] - fa["median_s"] > max(fa["spread_s"], sb["spread_s"]))
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
