@@ -527,6 +527,141 @@ def test_hip_split_phase_entry_points_validate(hip):
     assert hip.glabc_propose(A.ALGO_GLMCMC, C.byref(g), C.byref(g), C.byref(es), C.byref(run), C.byref(io), None) == 0       # zero chains: nothing to do
     assert hip.glabc_select(A.ALGO_GLMCMC, C.byref(g), C.byref(es), C.byref(run), C.byref(io), None) == 0
     assert hip.glabc_model_simulate(None, buf.data_ptr(), None, 4, 0, 0, buf.data_ptr(), None) == -1
+    _walk_split_phase_refusals(hip)
+
+
+def _walk_split_phase_refusals(hip):
+    """Every row of pack_common (csrc/glabc_generic.hip) and of the three entry points' own NULL and range checks, one violated
+    condition per call on an otherwise valid call: the exact status, and every buffer any of the three could write -- chain state,
+    step io, history, streaming sums, the redraw counter -- still holds its canary afterwards."""
+    from helpers import assert_untouched, canary_f32, canary_f64, canary_i32, dev, host
+    n, N, d, yd, nd = 6, 3, 2, 2, 2
+    R, tri = N * n, d * (d + 1) // 2
+    sizes = dict(f32=dict(theta=d * n, y=yd * n, log_w=n, theta_prop=R * d, log_q=R, sim_noise=R * nd, log_u=n, prior_cur=n,
+                          kern_cur=n, history=d * n, y_prop=R * yd, prior_prop=R, kern_prop=R, q_cur=n, gf_chain=n),
+                 f64=dict(u_res=n, sum_theta=d * n, sum_outer=tri * n, sum_jump=tri * n),
+                 i32=dict(flags=n, n_moves=n, is_global=n, n_redrawn=1, n_valid=n, step_dev=1))
+    arenas, addr = {}, {}
+    for kind, fill, width in (("f32", canary_f32, 4), ("f64", canary_f64, 8), ("i32", canary_i32, 4)):
+        arenas[kind] = dev(fill(sum(sizes[kind].values())))
+        off = 0
+        for k, sz in sizes[kind].items():
+            addr[k] = arenas[kind].data_ptr() + off * width
+            off += sz
+
+    class Call:
+        def __init__(self):
+            p = addr.get
+            self.cs = A.Chains(n, 0, n, p("theta"), p("y"), p("log_w"), p("flags"), p("n_moves"), None, None, None, None)
+            self.mom = A.Moments(p("sum_theta"), p("sum_outer"), p("sum_jump"))
+            self.run = A.Run()
+            r = self.run
+            r.seed, r.step0, r.n_steps, r.global_frequency, r.batch_size = 1, 1, 1, 0.5, N
+            r.history, r.hist_stride, r.moments = p("history"), n, C.pointer(self.mom)
+            r.step0_device, r.global_frequency_per_chain = p("step_dev"), p("gf_chain")
+            self.io = A.StepIO(N, d, yd, nd, *[p(k) for k in ("theta_prop", "log_q", "sim_noise", "log_u", "u_res", "is_global", "y_prop",
+                                                                "prior_prop", "kern_prop", "prior_cur", "kern_cur", "q_cur", "n_valid")])
+            self.local = make_dist(("gauss", [0.0] * d, [0.3] * d)).descriptor()
+            self.glob = make_dist(("gauss", [0.1] * d, [1.2] * d)).descriptor()
+            self.algo, self.round, self.n_redrawn, self.null = A.ALGO_GLMCMC, 1, p("n_redrawn"), set()
+
+        def __call__(self, entry):
+            ref = lambda x: None if x is None else C.byref(x)                                  # noqa: E731
+            cs, run, io = [None if k in self.null else C.byref(getattr(self, k)) for k in ("cs", "run", "io")]
+            if entry == "propose":
+                return hip.glabc_propose(self.algo, ref(self.local), ref(self.glob), cs, run, io, None)
+            if entry == "redraw":
+                return hip.glabc_propose_redraw(ref(self.local), cs, run, io, self.round, self.n_redrawn, None)
+            return hip.glabc_select(self.algo, ref(self.glob), cs, run, io, None)
+
+    def field(obj, name, value):
+        return lambda s: setattr(getattr(s, obj), name, value)
+
+    def many(*fs):
+        return lambda s: [f(s) for f in fs]
+
+    def elem(obj, arr, value):
+        def f(s):
+            getattr(getattr(s, obj), arr)[0] = value
+        return f
+
+    def gamma(obj, shape0):
+        def f(s):
+            setattr(s, obj, make_dist(("gamma", [2.0] * d, [1.0] * d)).descriptor())
+            getattr(s, obj).p0[0] = shape0
+        return f
+
+    NUL, DIM, KIND, ARG = -1, -2, -3, -4
+    inf, nan = float("inf"), float("nan")
+    common = [
+        ("chains NULL", lambda s: s.null.add("cs"), NUL), ("run NULL", lambda s: s.null.add("run"), NUL),
+        ("io NULL", lambda s: s.null.add("io"), NUL),
+        ("theta_dim 0", field("io", "theta_dim", 0), DIM), ("y_dim 0", field("io", "y_dim", 0), DIM),
+        ("noise_dim -1", field("io", "noise_dim", -1), DIM),
+        ("n_prop 0", field("io", "n_prop", 0), ARG),
+        ("n_prop * n_chains > 2^40", many(field("cs", "n_chains", 2 ** 40), field("cs", "stride", 2 ** 40), field("run", "hist_stride", 2 ** 40),
+                                          field("io", "n_prop", 2)), ARG),
+        ("n_steps 0", field("run", "n_steps", 0), ARG), ("n_steps 2", field("run", "n_steps", 2), ARG),
+        ("a tape", lambda s: setattr(s.run, "tape", C.pointer(A.Tape())), ARG),
+        ("math_mode fast", field("run", "math_mode", 1), ARG),
+        ("dump_draws", lambda s: setattr(s.run, "dump_draws", C.pointer(A.DrawsOut())), ARG),
+        ("n_chains -1", field("cs", "n_chains", -1), ARG), ("stride < n_chains", field("cs", "stride", n - 1), ARG),
+        ("chain0 -1", field("cs", "chain0", -1), ARG),
+        ("theta NULL", field("cs", "theta", None), NUL), ("y NULL", field("cs", "y", None), NUL),
+        ("NaN global_frequency", field("run", "global_frequency", nan), ARG),
+        ("hist_stride < n_chains", field("run", "hist_stride", n - 1), ARG),
+        ("moments.sum_theta NULL", field("mom", "sum_theta", None), NUL), ("moments.sum_outer NULL", field("mom", "sum_outer", None), NUL),
+        ("moments.sum_jump NULL", field("mom", "sum_jump", None), NUL),
+    ]
+
+    def dist_rows(obj, allow_gamma):
+        rows = [(obj + " of another dim", field(obj, "dim", d + 1), DIM), (obj + " dim 0", field(obj, "dim", 0), DIM),
+                (obj + " dim 9", field(obj, "dim", 9), DIM),
+                ("theta_dim 9 with the descriptor " + obj, field("io", "theta_dim", 9), DIM),
+                (obj + " of an unknown kind", field(obj, "kind", 7), KIND),
+                (obj + " with an infinite loc", elem(obj, "p0", inf), ARG), (obj + " with a NaN log_scale", elem(obj, "p1", nan), ARG),
+                (obj + " with scale 0", elem(obj, "p2", 0.0), ARG), (obj + " with a NaN c0", field(obj, "c0", nan), ARG)]
+        if allow_gamma:
+            rows += [(obj + " Gamma with shape 0", gamma(obj, 0.0), ARG), (obj + " Gamma with a NaN gammaln", many(gamma(obj, 2.0), elem(obj, "p3", nan)), ARG)]
+        else:
+            rows += [(obj + " is a Gamma", gamma(obj, 2.0), KIND)]
+        return rows
+
+    algo_rows = [("unknown algorithm", lambda s: setattr(s, "algo", 7), KIND), ("negative algorithm", lambda s: setattr(s, "algo", -1), KIND),
+                 ("GlobalMCMC with three candidates", lambda s: setattr(s, "algo", A.ALGO_GLOBALMCMC), ARG)]
+    null_io = lambda *names: [("io.%s NULL" % k, field("io", k, None), NUL) for k in names]                # noqa: E731
+    table = {
+        "propose": common + algo_rows + dist_rows("local", False) + dist_rows("glob", True) +
+        null_io("theta_prop", "log_q", "log_u", "u_res", "is_global") + [("noise_dim > 0 with sim_noise NULL", field("io", "sim_noise", None), NUL)],
+        "redraw": common + dist_rows("local", False) + null_io("theta_prop", "is_global", "prior_prop") + [
+            ("local NULL", lambda s: setattr(s, "local", None), NUL), ("n_redrawn NULL", lambda s: setattr(s, "n_redrawn", None), NUL),
+            ("round 0", lambda s: setattr(s, "round", 0), ARG), ("round -1", lambda s: setattr(s, "round", -1), ARG),
+            ("round 2^24 + 1", lambda s: setattr(s, "round", 2 ** 24 + 1), ARG)],
+        "select": common + algo_rows + dist_rows("glob", True) +
+        null_io("theta_prop", "log_q", "log_u", "u_res", "is_global", "y_prop", "prior_prop", "kern_prop", "prior_cur", "kern_cur") + [
+            ("GLMCMC without log_w", field("cs", "log_w", None), NUL), ("GLMCMC without flags", field("cs", "flags", None), NUL),
+            ("GLMALA without log_w", many(lambda s: setattr(s, "algo", A.ALGO_GLMALA), field("cs", "log_w", None)), NUL),
+            ("GLMALA without flags", many(lambda s: setattr(s, "algo", A.ALGO_GLMALA), field("cs", "flags", None)), NUL),
+            ("neither global nor q_cur", many(lambda s: setattr(s, "glob", None), field("io", "q_cur", None)), NUL)],
+    }
+    for entry, rows in table.items():
+        # the call the rows start from passes every check: with zero chains it returns GLABC_OK (and launches nothing)
+        ok = Call()
+        ok.cs.n_chains = 0
+        assert ok(entry) == 0, entry
+        for what, violate, status in rows:
+            call = Call()
+            violate(call)
+            assert call(entry) == status, (entry, what)
+            for a in arenas.values():
+                assert_untouched(host(a))
+    # the last valid round, and a callback proposal at theta_dim 9, are not refused (zero chains: nothing runs)
+    ok = Call()
+    ok.cs.n_chains, ok.round = 0, 2 ** 24
+    assert ok("redraw") == 0
+    ok = Call()
+    ok.cs.n_chains, ok.io.theta_dim, ok.local, ok.glob = 0, 9, None, None
+    assert ok("propose") == 0
 
 
 @pytest.mark.gpu
