@@ -144,8 +144,10 @@ inline int check_mix_model(const glabc_model* m, const glabc_mixture* g)
     return check_mixture(g, m->theta_dim);
 }
 
-inline int check_mix_run(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
-                         const glabc_run* r, bool isir)
+// what the stepping entry points of the mixture variant share, in one order; wide: the batch sizes and lanes per chain of the
+// lane-group kernel instead of the register kernels'
+inline int check_mix_steps(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
+                           const glabc_run* r, bool isir, bool wide)
 {
     if (int e = check_mix_model(m, g)) return e;
     if (int e = check_dist(local, m->theta_dim)) return e;
@@ -154,14 +156,30 @@ inline int check_mix_run(const glabc_model* m, const glabc_dist* local, const gl
     if (int e = check_chains(c, isir ? CHAINS_ISIR : CHAINS_PLAIN)) return e;
     if (r->n_steps < 0) return GLABC_ERR_ARG;
     if (int e = check_frequency(r)) return e;
-    if (isir && (r->batch_size < 1 || r->batch_size > GLABC_MAX_BATCH)) return GLABC_ERR_ARG;
-    if (r->lanes_per_chain != 0 && r->lanes_per_chain != 1) return GLABC_ERR_ARG;
+    const int n_lo = wide ? GLABC_MAX_BATCH + 1 : 1, n_hi = wide ? GLABC_MAX_BATCH_WIDE : GLABC_MAX_BATCH;
+    if (isir && (r->batch_size < n_lo || r->batch_size > n_hi)) return GLABC_ERR_ARG;
+    if (wide ? check_lanes_wide(r->lanes_per_chain) != GLABC_OK : (r->lanes_per_chain != 0 && r->lanes_per_chain != 1)) return GLABC_ERR_ARG;
     if (int e = check_history(r, c->n_chains)) return e;
     if (int e = check_moments(r)) return e;
     if (int e = check_step_counter(r)) return e;
     if (r->step0_device) return GLABC_ERR_ARG;                  // the split-phase entry points only
     if (r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
     return GLABC_OK;
+}
+
+// glabc_glmcmc_mix_steps (isir: batch sizes 1..GLABC_MAX_BATCH) / glabc_globalmcmc_mix_steps: one lane per chain
+inline int check_mix_run(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
+                         const glabc_run* r, bool isir)
+{
+    return check_mix_steps(m, local, g, c, r, isir, false);
+}
+
+// glabc_glmcmc_mix_wide_steps: batch sizes GLABC_MAX_BATCH + 1..GLABC_MAX_BATCH_WIDE in lane groups of 8 / 16 / 32 / 64 (0: the
+// library chooses); the rest of the matrix is check_mix_run's
+inline int check_mix_wide_run(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
+                              const glabc_run* r)
+{
+    return check_mix_steps(m, local, g, c, r, true, true);
 }
 
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------

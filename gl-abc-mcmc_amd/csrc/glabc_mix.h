@@ -34,6 +34,12 @@ inline MixArgs<D> pack_mixture(const glabc_mixture* g)
 template <int D, int YD>
 int launch_mix_dim(int algo, int n_batch, const MixStepArgs<D, YD>& a, hipStream_t stream);
 
+// GLMCMC at n_batch GLABC_MAX_BATCH + 1..GLABC_MAX_BATCH_WIDE: the lane-group kernel's mixture variant (glabc_wide.h) at
+// lanes = 8 / 16 / 32 / 64 lanes per chain; defined in glabc_wide_mix.hip.  GLABC_ERR_LAUNCH where the device cannot give a
+// workgroup its LDS rows (nothing is launched).
+template <int D, int YD>
+int launch_wide_mix(const MixStepArgs<D, YD>& a, int n_batch, int lanes, hipStream_t stream);
+
 // GLMCMC.py:52-55 with the mixture as the importance proposal
 template <int D, int YD>
 int launch_init_weights_mix_dim(const MixStepArgs<D, YD>& a, hipStream_t stream);

@@ -1,7 +1,7 @@
 // glabc_mix.hip -- GaussianMixture (distribution.py:206-293; the specification is in include/glabc.h): the row-wise kernels
 // glabc_mixture_log_prob / glabc_mixture_forward and the C entry points of the samplers' mixture variant, whose kernels live
-// in glabc_mix_dim.hip.  Geometry is fixed (one lane per chain, default schedule): these entry points do not go through the
-// launch plan.
+// in glabc_mix_dim.hip (one lane per chain, default schedule) and glabc_wide_mix.hip (lane groups, batch sizes above
+// GLABC_MAX_BATCH).  The entry point names the kernel: these entry points do not go through the launch plan.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -108,6 +108,21 @@ static int run_mix_sampler(int algo, const glabc_model* m, const glabc_dist* loc
     });
 }
 
+// batch sizes beyond the register kernels: lane groups of a wavefront share a chain's candidates (glabc_wide_mix.hip)
+static int run_mix_wide(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c, const glabc_run* r,
+                        void* stream)
+{
+    if (int e = check_mix_wide_run(m, local, g, c, r)) return e;
+    if (c->n_chains == 0 || r->n_steps == 0) return GLABC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int N = r->batch_size, lanes = r->lanes_per_chain ? r->lanes_per_chain : wide_default_lanes(N);
+    if (m->sim_kind == GLABC_SIM_GK) return launch_wide_mix<4, 8>(pack_mix_args<4, 8>(m, local, g, c, r), N, lanes, s);
+    return dispatch_range<1, 4>(m->theta_dim, GLABC_ERR_KIND, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return launch_wide_mix<D, D>(pack_mix_args<D, D>(m, local, g, c, r), N, lanes, s);
+    });
+}
+
 template <bool FORWARD>
 static int run_mix_rows(const glabc_mixture* g, const double* z, int64_t n, uint64_t seed, int64_t row0, double* z_out, double* out,
                         void* stream)
@@ -171,6 +186,13 @@ __attribute__((visibility("default"))) int glabc_glmcmc_mix_steps(const glabc_mo
                                                                   const glabc_run* run, void* stream)
 {
     return run_mix_sampler(ALGO_GLMCMC, model, local, importance, chains, run, stream);
+}
+
+__attribute__((visibility("default"))) int glabc_glmcmc_mix_wide_steps(const glabc_model* model, const glabc_dist* local,
+                                                                       const glabc_mixture* importance, const glabc_chains* chains,
+                                                                       const glabc_run* run, void* stream)
+{
+    return run_mix_wide(model, local, importance, chains, run, stream);
 }
 
 __attribute__((visibility("default"))) int glabc_globalmcmc_mix_steps(const glabc_model* model, const glabc_dist* local,

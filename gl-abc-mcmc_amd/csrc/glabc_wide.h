@@ -21,6 +21,11 @@
 // The local move (GLMCMC.py:90-104) is candidate 0 evaluated as theta + increment by every lane of the group.  State is
 // replicated over the group's lanes (registers); lane 0 writes history, sums and the final state.  Results equal the CPU
 // checker's bit for bit for every L, like the register kernels' (tests/test_hip_parity.py).
+//
+// MX: the importance proposal is a GaussianMixture (glabc_mixture, include/glabc.h; glabc_wide_mix.hip).  The argument block is
+// then a MixStepArgs, the kernel's first argument so that mix_of finds the tables in the kernel-argument segment; a global
+// candidate's theta' / log q' and every log q of a state come from the mixture, and nothing else differs.  The run-time
+// compiled programs do not instantiate it.
 #pragma once
 
 #include "glabc_geometry.h"     // WIDE_BLOCK, the group row in LDS
@@ -32,12 +37,18 @@ struct Cand {
     float lw, wl, pr, kk, log_acc;
 };
 
+// the argument block of the kernel: StepArgs, followed by the mixture's tables in the mixture variant
+template <int D, int YD, bool MX>
+using WideArgs = KernelArgs<D, YD, MX ? VAR_MIX : VAR_GENERIC>;
+
 // candidate j of (chain, step): the arithmetic of chain_step's generic variant for one slot -- ND = NoiseDim<YD> simulator
 // normals from word DP on (YD for the built-in simulators, the declared count for a run-time compiled one), and the prior
 // through model_prior (the user's hook where a run-time compiled source announces one)
 // GM: the instantiation also knows GLABC_DIST_GAMMA as importance proposal / prior (chain_step's VAR_GAMMA)
-template <int D, int YD, bool GM>
-GLABC_DEV Cand eval_candidate(const StepArgs<D, YD>& a, const Rng& rng, uint32_t step, int j, bool loc, const Chain<D, YD>& c,
+// MX: candidate j of a chain on the global branch is GaussianMixture.forward from the candidate's proposal normals (words
+// 0..D-1) and Philox slot GLABC_SLOT_MIX + j; every log q is the mixture's (chain_step's VAR_MIX)
+template <int D, int YD, bool GM, bool MX = false>
+GLABC_DEV Cand eval_candidate(const typename WideArgs<D, YD, MX>::type& a, const Rng& rng, uint32_t step, int j, bool loc, const Chain<D, YD>& c,
                               float (&th)[D], float (&yy)[YD])
 {
     constexpr int ND = NoiseDim<YD>::value;
@@ -74,7 +85,28 @@ GLABC_DEV Cand eval_candidate(const StepArgs<D, YD>& a, const Rng& rng, uint32_t
             for (int q = 0; q < D; ++q) th[q] = loc ? th[q] : tg[q];
         }
     }
-    const float lq = loc ? dist_log_prob<D, false, GM>(a.global, th) : (g_gam ? lq_gamma : dist_forward_log_p<D>(a.global, e));
+    float lq;
+    if constexpr (MX) {
+        // A wavefront holds chains on both branches: each lane forms its double variate first -- the drawn z, theta' = (float) z,
+        // or the local candidate (double) theta' -- and the K-mode density is then issued once for both.
+        // (float) log_prob((double) theta') is dist_mix_log_prob by definition.
+        const MixArgs<D>& mix = mix_of<D, YD>(a);
+        double z[D];
+#pragma unroll
+        for (int q = 0; q < D; ++q) z[q] = (double)th[q];
+        if (!loc) {
+            float eps[D];
+#pragma unroll
+            for (int q = 0; q < D; ++q) eps[q] = nrm[q];                      // the normals, whatever the local increment's kind
+            const glabc_u32x4 o = glabc_philox4x32_10(rng.c0, rng.c1, step, GLABC_SLOT_MIX + (uint32_t)j, rng.k0, rng.k1);
+            mix_draw<D>(mix, glabc_uniform_f64(o.v[0], o.v[1]), eps, z);      // dist_mix_forward's draw
+#pragma unroll
+            for (int q = 0; q < D; ++q) th[q] = (float)z[q];
+        }
+        lq = (float)mix_log_prob<D>(mix, z);
+    } else {
+        lq = loc ? dist_log_prob<D, false, GM>(a.global, th) : (g_gam ? lq_gamma : dist_forward_log_p<D>(a.global, e));
+    }
     model_simulate<D, YD>(a, th, s, yy);                                      // GLMCMC.py:71,94
     Cand r;
     r.pr = model_prior<D, YD, false, GM>(a, th);
@@ -101,9 +133,10 @@ GLABC_DEV int grp_get_i(int v, int src_sub)
     return __shfl(v, (lane & ~(L - 1)) | src_sub, 64);
 }
 
-template <int D, int YD, int L, bool GM>
-__global__ void __launch_bounds__(WIDE_BLOCK) wide_kernel(const StepArgs<D, YD> a, const int N)
+template <int D, int YD, int L, bool GM, bool MX = false>
+__global__ void __launch_bounds__(WIDE_BLOCK) wide_kernel(const typename WideArgs<D, YD, MX>::type a, const int N)
 {
+    static_assert(!(GM && MX), "the mixture variant knows no Gamma (prior or proposal)");
     extern __shared__ __attribute__((aligned(16))) float wide_lds[];
     constexpr int GROUPS = WIDE_BLOCK / L;
     const int sub = (int)(threadIdx.x % L), grp = (int)(threadIdx.x / L);
@@ -125,6 +158,7 @@ __global__ void __launch_bounds__(WIDE_BLOCK) wide_kernel(const StepArgs<D, YD> 
     c.n_moves = a.n_moves ? a.n_moves[i] : 0u;
     c.gf = a.gf_chain ? a.gf_chain[i] : a.gf;
     refresh_cache<D, YD, GM>(a, c);
+    if constexpr (MX) c.q = dist_mix_log_prob<D>(mix_of<D, YD>(a), c.theta);               // the placeholder's q is never read
     c.lw_cur = (c.flags & GLABC_FLAG_LOCAL) ? (c.prior + c.kern) - c.q : c.log_w;          // GLMCMC.py:60-64
     {
         const float v = glabc_expf(c.lw_cur);
@@ -180,7 +214,7 @@ __global__ void __launch_bounds__(WIDE_BLOCK) wide_kernel(const StepArgs<D, YD> 
         for (int r = 0; r < rounds; ++r) {
             const int j = is_global ? sub + L * r : 0;                  // a chain on the local branch: candidate 0, every lane
             if ((is_global && j < N) || (!is_global && r == 0)) {
-                cd = eval_candidate<D, YD, GM>(a, rng, step, j, !is_global, c, th, yy);
+                cd = eval_candidate<D, YD, GM, MX>(a, rng, step, j, !is_global, c, th, yy);
                 if (is_global) w[1 + j] = cd.wl;
             }
         }
@@ -271,7 +305,7 @@ __global__ void __launch_bounds__(WIDE_BLOCK) wide_kernel(const StepArgs<D, YD> 
             if (rounds_all > 1 && __any(moved && is_global)) {
                 // several candidates per lane: every lane re-evaluates the winner (same counter, same bits)
                 float th2[D], yy2[YD];
-                const Cand c2 = eval_candidate<D, YD, GM>(a, rng, step, moved && is_global ? ind - 1 : 0, false, c, th2, yy2);
+                const Cand c2 = eval_candidate<D, YD, GM, MX>(a, rng, step, moved && is_global ? ind - 1 : 0, false, c, th2, yy2);
                 if (moved && is_global) {
 #pragma unroll
                     for (int q = 0; q < D; ++q) th[q] = th2[q];
@@ -287,7 +321,10 @@ __global__ void __launch_bounds__(WIDE_BLOCK) wide_kernel(const StepArgs<D, YD> 
                 for (int q = 0; q < YD; ++q) c.y[q] = yy[q];
                 c.prior = cd.pr;
                 c.kern = cd.kk;
-                c.q = dist_log_prob<D, false, GM>(a.global, c.theta);
+                if constexpr (MX)
+                    c.q = dist_mix_log_prob<D>(mix_of<D, YD>(a), c.theta);
+                else
+                    c.q = dist_log_prob<D, false, GM>(a.global, c.theta);
                 c.lw_cur = cd.lw;
                 c.w_cur = cd.wl;
                 if (is_global)

@@ -20,8 +20,9 @@ shape; batch_size <= 4096) run in the fused kernels (above 16 proposals lane gro
 ``distribution.Gamma`` prior or importance proposal is fused on the |theta| + noise Model up to theta_dim 4, on g-and-k
 (``GK_set(prior=...)``) and on a ``CompiledModel`` (its programs are then compiled with the Gamma kernels); a Gamma local increment
 is a callback and runs split-phase.  A ``distribution.GaussianMixture`` importance proposal (up to 8 modes) is fused on the
-|theta| + noise Model up to theta_dim 4 and on g-and-k for batch_size <= 16 with a DiagGaussian / Uniform prior: ``"auto"`` then draws
-it from the kernel's Philox stream instead of torch's generator (the same law); ``path="generic"`` keeps the callback.  A
+|theta| + noise Model up to theta_dim 4 and on g-and-k with a DiagGaussian / Uniform prior, at every batch_size up to 4096 (up to 16
+proposals ``glabc_glmcmc_mix_steps``, above ``glabc_glmcmc_mix_wide_steps``, the lane-group kernel's mixture variant): ``"auto"`` then
+draws it from the kernel's Philox stream instead of torch's generator (the same law); ``path="generic"`` keeps the callback.  A
 ``compiled.CompiledModel`` (a user's simulator compiled into those kernels at run time) runs fused as well: up to 16 proposals in a register kernel
 compiled for the batch size, 17..4096 in the lane-group kernel compiled once per Model -- except that ``"auto"`` keeps one with a
 user prior on the split-phase path above 16 proposals (only that path redraws the 7 log(1e-10) prior sentinel), and falls back
@@ -51,7 +52,8 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
     # fast_math names the fused kernel's variant: "auto" takes the fused path for it unconditionally
     fused = path == "fused" or (path == "auto" and (fast_math or generic.fused_supported(ABCset, (Local_Proposal, Importance_Proposal),
                                                                                          batch_size, _capi.MAX_BATCH_WIDE, gamma_ok=True,
-                                                                                         mixture_ok=True)))
+                                                                                         mixture_ok=True,
+                                                                                         mixture_max_batch=_capi.MAX_BATCH_WIDE)))
     rtc = None
     if fused and path == "auto" and not fast_math and int(batch_size) > _capi.MAX_BATCH and \
             getattr(generic.try_descriptor(ABCset), "sim_kind", None) == _capi.SIM_USER:
@@ -83,7 +85,10 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
             rtc = generic.rtc_program(ABCset, model, Importance_Proposal, _capi.ALGO_GLMCMC, batch_size)
     else:
         engine.init_weights(model, imp, chains)                    # GLMCMC.py:52-55
-    engine.run_steps("glabc_glmcmc_mix_steps" if mix else "glabc_glmcmc_steps", model, local, imp, chains, num_ite - 1, 1, engine.draw_seed(seed),
+    entry = "glabc_glmcmc_steps"
+    if mix:                                                        # above the register kernels' batch sizes: lane groups
+        entry = "glabc_glmcmc_mix_wide_steps" if int(batch_size) > _capi.MAX_BATCH else "glabc_glmcmc_mix_steps"
+    engine.run_steps(entry, model, local, imp, chains, num_ite - 1, 1, engine.draw_seed(seed),
                      global_frequency, batch_size, history=None if hist is None else hist[1:], moments=stats,
                      steps_per_launch=steps_per_launch, rtc_program=rtc, mirror=mirror,
                      math_mode=_capi.MATH_FAST if fast_math else _capi.MATH_EXACT)

@@ -309,6 +309,7 @@ ENTRY_POINTS = {
     "glabc_init_weights_mix": (C.c_int, [_P(Model), _P(Mixture), _P(Chains), C.c_void_p]),
     "glabc_glmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_globalmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
+    "glabc_glmcmc_mix_wide_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_model_prior_log_prob": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_model_discrepancy": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_model_log_kernel": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -135,12 +135,12 @@ def run_steps(entry, model_desc, local_desc, global_desc, chains, n_steps, step0
               history=None, moments=None, steps_per_launch=None, lanes_per_chain=0, debug_flags=0, gf_per_chain=None,
               rtc_program=None, math_mode=0, dump_draws=None, mirror=None):
     """Advance `chains` by n_steps iterations with the C-ABI entry point `entry`
-    ('glabc_glmcmc_steps' / 'glabc_globalmcmc_steps', or their '_mix_steps' twins when global_desc is a _capi.Mixture), K
-    iterations per launch.
+    ('glabc_glmcmc_steps' / 'glabc_globalmcmc_steps', or their '_mix_steps' twins when global_desc is a _capi.Mixture --
+    'glabc_glmcmc_mix_wide_steps' for GLMCMC batch sizes above MAX_BATCH), K iterations per launch.
 
     history: None or float32 tensor [n_steps][d][C] on the chains' device.
-    lanes_per_chain: 0 = let the library choose from the chain count; 1 / 2 / 4 force the
-    launch geometry (results are identical for every choice).
+    lanes_per_chain: 0 = let the library choose from the chain count; 1 / 2 / 4 (batch sizes above MAX_BATCH: 8 / 16 / 32 / 64)
+    force the launch geometry (results are identical for every choice).
     gf_per_chain: None or float32 device tensor [C] replacing global_frequency chain by chain.
     rtc_program: handle of glabc_rtc_compile -- the launches then go to glabc_rtc_steps (a Model whose simulator was compiled
     into the kernel at run time, compiled.CompiledModel) with the same arguments.

@@ -14,7 +14,7 @@ one iteration for ALL chains is
 
 so the decisions are taken by the same arithmetic as in the fused kernels, and the Model is called
 ``batch_size * n_chains`` rows at a time instead of ``batch_size`` rows.  Proposal objects without a ``glabc_dist``
-descriptor (``GaussianMixture``, a user's class; a ``Gamma`` as the local increment) are callbacks too: ``forward`` / ``sample`` /
+descriptor (a user's class; a ``Gamma`` as the local increment; a ``GaussianMixture`` outside ``fused_supported``'s matrix) are callbacks too: ``forward`` / ``sample`` /
 ``log_prob``.  A ``Gamma`` prior or importance / global proposal is no reason to come here: the fused kernels take it on the
 |theta| + noise Model up to theta_dim 4, on g-and-k and on a ``CompiledModel`` (``fused_supported``).
 
@@ -73,14 +73,16 @@ def rtc_program(ABCset, model_desc, proposal, algo, batch_size=1):
     return ABCset.program(algo, batch_size)
 
 
-def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, gamma_ok=False, mixture_ok=False):
+def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, gamma_ok=False, mixture_ok=False, mixture_max_batch=None):
     """Can the fused kernels (glabc_glmcmc_steps / glabc_globalmcmc_steps / glabc_glmala_steps) run this configuration?
     gamma_ok: the entry point knows GLABC_DIST_GAMMA as the LAST proposal (importance / global) and as the Model's prior --
     GLMCMC and GlobalMCMC on the |theta| + noise Model up to theta_dim 4, on g-and-k and on a compiled.CompiledModel, whose
     programs are then compiled with GLABC_RTC_GAMMA (include/glabc.h).
     mixture_ok: the caller has the mixture entry points (glabc_glmcmc_mix_steps / glabc_globalmcmc_mix_steps): a
     distribution.GaussianMixture (a _capi.Mixture descriptor) as the LAST proposal, on the |theta| + noise Model up to theta_dim 4
-    and on g-and-k, batch sizes up to GLABC_MAX_BATCH, no Gamma prior; anywhere else a mixture stays a callback."""
+    and on g-and-k, batch sizes up to GLABC_MAX_BATCH, no Gamma prior; anywhere else a mixture stays a callback.
+    mixture_max_batch: the largest batch size the caller's mixture entry points take, where that is more than GLABC_MAX_BATCH (GLMCMC:
+    glabc_glmcmc_mix_wide_steps, GLABC_MAX_BATCH_WIDE); the rest of the mixture's matrix is the same."""
     m = try_descriptor(ABCset)
     if m is None or not isinstance(m, _capi.Model):
         return False
@@ -90,7 +92,7 @@ def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, ga
         if isinstance(d, _capi.Mixture):
             return bool(mixture_ok and i == len(proposals) - 1 and i > 0 and d.dim == m.theta_dim and not gamma and
                         ((m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4) or m.sim_kind == _capi.SIM_GK) and
-                        (batch_size is None or 1 <= int(batch_size) <= _capi.MAX_BATCH))
+                        (batch_size is None or 1 <= int(batch_size) <= (mixture_max_batch or _capi.MAX_BATCH)))
         if d is None or not isinstance(d, _capi.Dist) or d.dim != m.theta_dim:
             return False
         if d.kind == _capi.DIST_GAMMA:

@@ -587,7 +587,13 @@ int glabc_gamma_forward(const glabc_gamma* dist, int64_t n, uint64_t seed, int64
  * history, moments, global_frequency_per_chain and GLABC_DEBUG_EXACT_INDEX; one lane per chain in the default schedule
  * (lanes_per_chain 0 or 1).  Refused: theta_dim 5..8 and a Gamma prior (GLABC_ERR_KIND), a tape and GLABC_MATH_FAST
  * (GLABC_ERR_ARG), n_modes outside 1..GLABC_MAX_MODES (GLABC_ERR_ARG), dim != theta_dim (GLABC_ERR_DIM), a scale or inv_scale
- * that is not finite and > 0, a non-monotone cum_weight or a last cum_weight outside (0, 1 + 1e-9] (GLABC_ERR_ARG). */
+ * that is not finite and > 0, a non-monotone cum_weight or a last cum_weight outside (0, 1 + 1e-9] (GLABC_ERR_ARG).
+ * Batch sizes GLABC_MAX_BATCH + 1..GLABC_MAX_BATCH_WIDE of GLMCMC (glabc_glmcmc_mix_wide_steps): the same matrix, refusals and
+ * order of checks, in the lane-group kernel -- lanes_per_chain 0 (wide_default_lanes: 8 / 16 / 32 / 64 for a batch size up to 64 /
+ * 128 / 256 / above) or 8 / 16 / 32 / 64, anything else and a batch size outside that range, 1..GLABC_MAX_BATCH included, is
+ * GLABC_ERR_ARG; a launch whose group rows (4 (256 / lanes) (batch_size + 33) bytes of LDS) the device cannot give a workgroup is
+ * GLABC_ERR_LAUNCH and launches nothing.  Candidate j reads the same slots and words at every batch size (GLABC_SLOT_MIX + j,
+ * j < 4096); glabc_init_weights_mix serves both entry points. */
 #define GLABC_MAX_MODES 8
 typedef struct glabc_mixture {
     int32_t n_modes;               /* 1..GLABC_MAX_MODES */
@@ -616,6 +622,8 @@ int glabc_glmcmc_mix_steps(const glabc_model* model, const glabc_dist* local, co
                            const glabc_chains* chains, const glabc_run* run, void* stream);
 int glabc_globalmcmc_mix_steps(const glabc_model* model, const glabc_dist* local, const glabc_mixture* global,
                                const glabc_chains* chains, const glabc_run* run, void* stream);
+int glabc_glmcmc_mix_wide_steps(const glabc_model* model, const glabc_dist* local, const glabc_mixture* importance,
+                                const glabc_chains* chains, const glabc_run* run, void* stream);
 
 /* Model callbacks on n row-major points (Mixture.py:28-45): used by the host
  * mirror's Model class and by the parity tests. */

@@ -1,12 +1,14 @@
 """GLMCMC on Mixture_set with a four-mode GaussianMixture importance proposal: whole calls of
-  (a) path="auto"     the fused mixture kernel (glabc_glmcmc_mix_steps),
+  (a) path="auto"     the fused mixture kernel (glabc_glmcmc_mix_steps up to 16 proposals, glabc_glmcmc_mix_wide_steps above),
   (b) path="generic"  the split-phase path with the mixture as a callback -- what such a call ran before the kernel existed,
   (c) the fused kernel with a DiagGaussian importance proposal, as context,
 timed with a host clock that ends in a device synchronise.  After a warm-up of each, (a) and (b) alternate in one process;
 the median and the spread (max - min) of the repeats are reported, and (a) beats (b) only if the medians differ by more than
-both spreads.
+both spreads.  --split-iters gives (b) a shorter call of its own (it is three orders of magnitude slower); the comparison is then
+one of seconds per iteration, and each entry names its own iteration count.
 
-    python tools/mixture_bench.py [--chains 65536] [--iters 2000] [--batch 5] [--repeats 3] [--out profiles/mixture_bench.json]
+    python tools/mixture_bench.py [--chains 65536] [--iters 2000] [--split-iters ITERS] [--batch 5] [--repeats 3]
+                                  [--out profiles/mixture_bench.json]
 """
 import argparse
 import json
@@ -35,6 +37,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chains", type=int, default=65536)
     ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--split-iters", type=int, default=None, help="iterations of a split-phase call (default: --iters)")
     ap.add_argument("--batch", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup-iters", type=int, default=20)
@@ -53,7 +56,8 @@ def main():
     def call(ip, path, iters):
         return lambda: g.GLMCMC(model, iters + 1, th0, y0, lp, None, 0.9, ip, a.batch, path=path, **kw)
 
-    runs = {"fused_mixture": call(mix, "auto", a.iters), "split_phase_mixture": call(mix, "generic", a.iters),
+    iters = {"fused_mixture": a.iters, "split_phase_mixture": a.split_iters or a.iters, "fused_diag_gaussian": a.iters}
+    runs = {"fused_mixture": call(mix, "auto", a.iters), "split_phase_mixture": call(mix, "generic", iters["split_phase_mixture"]),
             "fused_diag_gaussian": call(gauss, "auto", a.iters)}
     for name, (ip, path) in {"fused_mixture": (mix, "auto"), "split_phase_mixture": (mix, "generic"),
                              "fused_diag_gaussian": (gauss, "auto")}.items():
@@ -62,15 +66,18 @@ def main():
     for _ in range(a.repeats):                               # (a) and (b) alternate; (c) rides along
         for name in ("fused_mixture", "split_phase_mixture", "fused_diag_gaussian"):
             times[name].append(clocked(runs[name]))
-    steps = float(a.chains) * a.iters
     res = {"workload": "GLMCMC on Mixture_set, theta_dim 2, 4-mode GaussianMixture importance proposal", "chains": a.chains,
            "iterations": a.iters, "batch_size": a.batch, "repeats": a.repeats, "device": torch.cuda.get_device_name(0)}
     for name, ts in times.items():
-        res[name] = {"seconds": ts, "median_s": statistics.median(ts), "spread_s": max(ts) - min(ts),
-                     "chain_steps_per_s": steps / statistics.median(ts)}
-    fa, sb = res["fused_mixture"], res["split_phase_mixture"]
-    res["fused_over_split_phase"] = sb["median_s"] / fa["median_s"]
-    res["fused_beats_split_phase_by_more_than_the_spread"] = bool(sb["median_s"] - fa["median_s"] > max(fa["spread_s"], sb["spread_s"]))
+        k = float(iters[name])
+        res[name] = {"iterations": iters[name], "seconds": ts, "median_s": statistics.median(ts), "spread_s": max(ts) - min(ts),
+                     "median_s_per_iteration": statistics.median(ts) / k, "spread_s_per_iteration": (max(ts) - min(ts)) / k,
+                     "chain_steps_per_s": a.chains * k / statistics.median(ts)}
+    fa, sb, dg = res["fused_mixture"], res["split_phase_mixture"], res["fused_diag_gaussian"]
+    res["fused_over_split_phase"] = sb["median_s_per_iteration"] / fa["median_s_per_iteration"]
+    res["fused_beats_split_phase_by_more_than_the_spread"] = bool(
+        sb["median_s_per_iteration"] - fa["median_s_per_iteration"] > max(fa["spread_s_per_iteration"], sb["spread_s_per_iteration"]))
+    res["fused_mixture_over_fused_diag_gaussian_time"] = fa["median_s"] / dg["median_s"]
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
