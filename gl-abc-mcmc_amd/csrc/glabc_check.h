@@ -182,6 +182,24 @@ inline int check_mix_wide_run(const glabc_model* m, const glabc_dist* local, con
     return check_mix_steps(m, local, g, c, r, true, true);
 }
 
+// ---- glabc_propose_mix: the mixture's checks in the order glabc_glmcmc_mix_steps makes them (the mixture, the local increment, the
+// pointers, a tape), ahead of glabc_propose's own, which the entry point makes next.  io gives the dimension the mixture must have;
+// local may be null as for glabc_propose (the caller then fills the local move's row); io->q_cur is written, so it must be there
+inline int check_propose_mix(int algo, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c, const glabc_run* r,
+                             const glabc_step_io* io)
+{
+    if (!io) return GLABC_ERR_NULL;
+    if (algo != GLABC_ALGO_GLMCMC && algo != GLABC_ALGO_GLOBALMCMC) return GLABC_ERR_KIND;
+    if (io->theta_dim < 1 || io->theta_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    if (int e = check_mixture(g, io->theta_dim)) return e;
+    if (local)
+        if (int e = check_dist(local, io->theta_dim)) return e;
+    if (!c || !r) return GLABC_ERR_NULL;
+    if (r->tape) return GLABC_ERR_ARG;                          // a tape has no mode draws
+    if (!io->q_cur) return GLABC_ERR_NULL;
+    return GLABC_OK;
+}
+
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------
 inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
                          const glabc_run* r)
@@ -204,6 +222,36 @@ inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_di
         if (r->tape || r->step0_device || (r->lanes_per_chain != 0 && r->lanes_per_chain != 1)) return GLABC_ERR_ARG;
     }
     if (r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
+    if (int e = check_frequency(r)) return e;
+    if (int e = check_history(r, c->n_chains)) return e;
+    if (int e = check_moments(r)) return e;
+    return check_step_counter(r);
+}
+
+// ---- glabc_rtc_mix_steps: a launch of the run-time compiled MIXTURE program of shape `p` ----------------------------------------
+// mix_program: the program was built from the mixture table (glabc_rtc_compile_mix / _wide_mix, glabc_rtc_mix_kernels.h); a program of
+// the other table holds no kernel that takes a MixStepArgs.  The order is the contract (include/glabc.h).
+inline int check_rtc_mix_run(const RtcShape& p, bool mix_program, const glabc_model* m, const glabc_dist* local, const glabc_mixture* g,
+                             const glabc_chains* c, const glabc_run* r)
+{
+    if (!m || !local || !g || !c || !r) return GLABC_ERR_NULL;
+    if (m->sim_kind != GLABC_SIM_USER) return GLABC_ERR_KIND;
+    if (m->theta_dim != p.theta_dim || m->y_dim != p.y_dim || m->noise.dim != p.noise_dim) return GLABC_ERR_DIM;
+    if (!mix_program) return GLABC_ERR_KIND;
+    if (m->prior.kind == GLABC_DIST_GAMMA) return GLABC_ERR_KIND;               // the mixture variant knows no Gamma
+    if (check_dist(&m->prior, p.theta_dim) || check_dist(local, p.theta_dim)) return GLABC_ERR_ARG;      // whatever the defect of a descriptor
+    if (!std::isfinite(m->kern_log_scale) || !(m->kern_scale > 0.0f) || !std::isfinite(m->kern_c0)) return GLABC_ERR_ARG;
+    if (r->tape || r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;      // a tape has no mode draws
+    if (int e = check_mixture(g, p.theta_dim)) return e;
+    if (int e = check_chains(c, p.algo == GLABC_ALGO_GLMCMC ? CHAINS_ISIR : CHAINS_PLAIN)) return e;
+    if (r->n_steps < 0 || r->step0_device) return GLABC_ERR_ARG;
+    if (p.wide) {                                                 // lane groups: batch sizes the register kernels do not hold
+        if (r->batch_size <= GLABC_MAX_BATCH || r->batch_size > GLABC_MAX_BATCH_WIDE) return GLABC_ERR_ARG;
+        if (check_lanes_wide(r->lanes_per_chain)) return GLABC_ERR_ARG;
+    } else {
+        if (p.algo == GLABC_ALGO_GLMCMC && r->batch_size != p.batch_size) return GLABC_ERR_ARG;      // compiled for one batch size
+        if (r->lanes_per_chain != 0 && r->lanes_per_chain != 1) return GLABC_ERR_ARG;
+    }
     if (int e = check_frequency(r)) return e;
     if (int e = check_history(r, c->n_chains)) return e;
     if (int e = check_moments(r)) return e;

@@ -887,18 +887,25 @@ GLABC_DEV bool chain_step(const typename KernelArgs<D, YD, VAR>::type& a, const 
     // ---- a GaussianMixture's N candidates and their log q: drawn in a loop of their own, ahead of the unrolled candidate
     // code, and staged in LDS (each lane reads back only what it wrote: no barrier).  The float64 density is then compiled
     // once instead of N times, and its temporaries are dead before the N candidates' registers fill.  A candidate's proposal
-    // normals are words 0..D-1 of its first block (D <= 4).
+    // normals are words 0..D-1 of its blocks: the first block up to theta_dim 4 (the built-in kernels), the first two above (a
+    // run-time compiled Model's, glabc_rtc_compile_mix).
     [[maybe_unused]] float* mix_stage = nullptr;
     if constexpr (MX) {
-        static_assert(D <= 4, "the mixture variant is instantiated up to theta_dim 4");
+        constexpr int PB = (D + 3) / 4;            // blocks that hold proposal words
+        static_assert(N * (D + 1) * 64 * 4 <= 64 * 1024, "the staged candidates fit a workgroup's LDS");
         __shared__ float mix_lds[N * (D + 1) * 64];
         mix_stage = mix_lds + (threadIdx.x & 63u);
 #pragma unroll 1
         for (int j = 0; j < N; ++j) {
             const glabc_u32x4 o = glabc_philox4x32_10(rng.c0, rng.c1, step, (uint32_t)(1 + j * SPP), rng.k0, rng.k1);
-            float nj[4], ej[D], tm[D], lqm;
+            float nj[4 * PB], ej[D], tm[D], lqm;
             glabc_normal_pair(o.v[0], o.v[1], &nj[0], &nj[1]);
             if constexpr (D > 2) glabc_normal_pair(o.v[2], o.v[3], &nj[2], &nj[3]);
+            if constexpr (D > 4) {
+                const glabc_u32x4 o1 = glabc_philox4x32_10(rng.c0, rng.c1, step, (uint32_t)(1 + j * SPP + 1), rng.k0, rng.k1);
+                glabc_normal_pair(o1.v[0], o1.v[1], &nj[4], &nj[5]);
+                if constexpr (D > 6) glabc_normal_pair(o1.v[2], o1.v[3], &nj[6], &nj[7]);
+            }
 #pragma unroll
             for (int q = 0; q < D; ++q) ej[q] = nj[q];
             dist_mix_forward<D>(mix_of(a), rng.c0, rng.c1, rng.k0, rng.k1, step, j, ej, tm, lqm);

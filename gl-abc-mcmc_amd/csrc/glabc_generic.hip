@@ -1,5 +1,5 @@
 // glabc_generic.hip -- the split-phase iteration for Models whose callbacks are arbitrary code (include/glabc.h,
-// "split-phase iteration"): glabc_propose, glabc_propose_redraw, glabc_select, glabc_model_simulate.
+// "split-phase iteration"): glabc_propose, glabc_propose_mix, glabc_propose_redraw, glabc_select, glabc_model_simulate.
 //
 // The fused sampler kernels (glabc_sampler.h) need the Model as numbers (a glabc_model).  The reference's plug-in API is
 // the duck-typed Model protocol (examples/Mixture.py:5-53): any object with generate_samples / prior_log_prob /
@@ -25,7 +25,9 @@
 
 #include "glabc_check.h"
 #include "glabc_device.h"
+#include "glabc_dispatch.h"
 #include "glabc_launch.h"
+#include "glabc_mix.h"
 
 namespace glabc {
 
@@ -139,17 +141,26 @@ GLABC_DEV void apply_proposal(const GenDist& g, const float (&e)[GD], const floa
     if (lq_out) *lq_out = g.kind == GLABC_DIST_DIAG_GAUSS ? g.c0 - rowsum_small(t, g.dim) : g.c0;
 }
 
-__global__ void __launch_bounds__(256) propose_kernel(const GenArgs a)
+// What candidate row r = j * n_chains + c draws, for propose_kernel and propose_mix_kernel alike: the step head on row 0 (written
+// to log_u / u_res / is_global), the proposal's noise e (uniforms for a Uniform proposal) and its words as normals whatever the
+// proposal (nrm: a GaussianMixture's), and the simulator's normals (written to sim_noise)
+struct RowDraws {
+    int j;
+    int64_t c;
+    uint32_t c0, c1, step;
+    bool is_global;
+    float e[GD], nrm[GD];
+};
+
+GLABC_DEV void propose_draws(const GenArgs& a, int64_t r, RowDraws& d)
 {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= a.n_chains * a.n_prop) return;
-    const int j = (int)(r / a.n_chains);
-    const int64_t c = r - (int64_t)j * a.n_chains;
+    const int j = d.j = (int)(r / a.n_chains);
+    const int64_t c = d.c = r - (int64_t)j * a.n_chains;
     const uint64_t gid = (uint64_t)(a.chain0 + c);
-    const uint32_t c0 = (uint32_t)gid, c1 = (uint32_t)(gid >> 32);
+    const uint32_t c0 = d.c0 = (uint32_t)gid, c1 = d.c1 = (uint32_t)(gid >> 32);
     const int D = a.theta_dim, DP = D + (D & 1), ND = a.noise_dim;
     const int SPP = (DP + ND + 3) / 4;
-    const uint32_t step = a.step_dev ? *a.step_dev : a.step;
+    const uint32_t step = d.step = a.step_dev ? *a.step_dev : a.step;
 
     bool is_global = true;
     if (j == 0) {                                                           // the step head, Philox slot 0
@@ -161,12 +172,13 @@ __global__ void __launch_bounds__(256) propose_kernel(const GenArgs a)
         a.log_u[c] = (ua == 0.0f) ? -__builtin_inff() : glabc_logf_normal(ua);   // GLMCMC.py:98
         a.u_res[c] = glabc_uniform_f64(h.v[2], h.v[3]);                     // GLMCMC.py:17
     }
+    d.is_global = is_global;
     const GenDist& g = is_global ? a.global : a.local;
     const bool uni = g.kind == GLABC_DIST_UNIFORM;
 
-    float e[GD];
+    float (&e)[GD] = d.e;
 #pragma unroll
-    for (int q = 0; q < GD; ++q) e[q] = 0.0f;
+    for (int q = 0; q < GD; ++q) e[q] = d.nrm[q] = 0.0f;
     float* noise_row = a.sim_noise ? a.sim_noise + r * ND : nullptr;
     // blocks 0 and 1 hold every proposal word (theta_dim <= 8): statically indexed
 #pragma unroll
@@ -180,6 +192,7 @@ __global__ void __launch_bounds__(256) propose_kernel(const GenArgs a)
             for (int t = 0; t < 4; ++t) {
                 const int gi = 4 * b + t;
                 if (gi < D) e[gi] = uni ? glabc_uniform_f32(o.v[t]) : nrm[t];
+                if (gi < D) d.nrm[gi] = nrm[t];
                 if (noise_row && gi >= DP && gi - DP < ND) noise_row[gi - DP] = nrm[t];
             }
         }
@@ -197,6 +210,20 @@ __global__ void __launch_bounds__(256) propose_kernel(const GenArgs a)
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(256) propose_kernel(const GenArgs a)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.n_chains * a.n_prop) return;
+    RowDraws d;
+    propose_draws(a, r, d);
+    const int j = d.j, D = a.theta_dim;
+    const int64_t c = d.c;
+    const uint32_t c0 = d.c0, c1 = d.c1, step = d.step;
+    const bool is_global = d.is_global;
+    const float (&e)[GD] = d.e;
+    const GenDist& g = is_global ? a.global : a.local;
     if (!g.present) return;                                                 // the caller fills this proposal's rows
     float* th_out = a.theta_prop + r * D;
     if (is_global && g.kind == GLABC_DIST_GAMMA) {                          // Gamma.forward on the chain's Gamma slots (include/glabc.h)
@@ -220,6 +247,56 @@ __global__ void __launch_bounds__(256) propose_kernel(const GenArgs a)
         apply_proposal(g, e, a.theta + c, a.stride, th_out, nullptr);       // GLMCMC.py:91 / GlobalMCMC.py:56
         a.log_q[r] = 0.0f;                                                  // unused by the local move
     }
+}
+
+// glabc_propose_mix: propose_kernel with no global descriptor, and the rows it leaves to the caller filled from a GaussianMixture
+// as the fused kernels' mixture variant fills them (dist_mix_forward, glabc_device.h): every row j > 0, and row 0 of a chain on the
+// global branch.  Row 0's work-item also writes q_cur = (float) log_prob((double) Theta_old).  The tables follow the GenArgs in the
+// argument block and are read where they lie in the kernel-argument segment, as mix_of reads them: the wave-uniform mode counter
+// is then the offset of a scalar load (indexing the by-value copy would put the block in scratch).
+template <int D>
+struct ProposeMixArgs {
+    GenArgs a;
+    float* q_cur;
+    MixArgs<D> mix;
+};
+
+template <int D>
+GLABC_DEV const MixArgs<D>& propose_mix_tables()
+{
+    const char* base = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(const MixArgs<D>*)(base + __builtin_offsetof(ProposeMixArgs<D>, mix));
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) propose_mix_kernel(const ProposeMixArgs<D> pa)
+{
+    const GenArgs& a = pa.a;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.n_chains * a.n_prop) return;
+    RowDraws d;
+    propose_draws(a, r, d);
+    const MixArgs<D>& mix = propose_mix_tables<D>();
+    float* th_out = a.theta_prop + r * D;
+    if (d.j == 0) {                                                         // Importance_Proposal.log_prob(Theta_old), GLMCMC.py:63
+        float cur[D];
+#pragma unroll
+        for (int q = 0; q < D; ++q) cur[q] = a.theta[q * a.stride + d.c];
+        pa.q_cur[d.c] = dist_mix_log_prob<D>(mix, cur);
+        if (!d.is_global) {                                                 // the local move's row, as propose_kernel writes it
+            if (!a.local.present) return;                                   // ... or leaves it to the caller
+            apply_proposal(a.local, d.e, a.theta + d.c, a.stride, th_out, nullptr);
+            a.log_q[r] = 0.0f;
+            return;
+        }
+    }
+    float eps[D], tm[D], lq;
+#pragma unroll
+    for (int q = 0; q < D; ++q) eps[q] = d.nrm[q];
+    dist_mix_forward<D>(mix, d.c0, d.c1, a.seed_lo, a.seed_hi, d.step, d.j, eps, tm, lq);
+#pragma unroll
+    for (int q = 0; q < D; ++q) th_out[q] = tm[q];
+    a.log_q[r] = lq;
 }
 
 // GLMCMC.py:92-93: a chain on the local branch whose proposal's prior is the sentinel 7*log(1e-10) redraws its increment
@@ -512,6 +589,29 @@ __attribute__((visibility("default"))) int glabc_propose(int algo, const glabc_d
     if (chains->n_chains == 0) return GLABC_OK;
     hipLaunchKernelGGL(propose_kernel, dim3(grid_for(chains->n_chains * io->n_prop, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
+}
+
+__attribute__((visibility("default"))) int glabc_propose_mix(int algo, const glabc_dist* local, const glabc_mixture* global,
+                                                             const glabc_chains* chains, const glabc_run* run,
+                                                             const glabc_step_io* io, void* stream)
+{
+    if (int e = check_propose_mix(algo, local, global, chains, run, io)) return e;
+    GenArgs a;
+    int rc = pack_common(algo, local, nullptr, chains, run, io, &a);      // glabc_propose(algo, local, NULL, ...)'s own checks
+    if (rc) return rc;
+    if (!io->theta_prop || !io->log_q || !io->log_u || !io->u_res || !io->is_global) return GLABC_ERR_NULL;
+    if (io->noise_dim > 0 && !io->sim_noise) return GLABC_ERR_NULL;
+    if (chains->n_chains == 0) return GLABC_OK;
+    return dispatch_range<1, GLABC_MAX_DIM>(io->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        ProposeMixArgs<D> pa;
+        std::memset(&pa, 0, sizeof pa);
+        pa.a = a;
+        pa.q_cur = const_cast<float*>(io->q_cur);           // an output here: glabc_select reads it
+        pa.mix = pack_mixture<D>(global);
+        hipLaunchKernelGGL((propose_mix_kernel<D>), dim3(grid_for(chains->n_chains * io->n_prop, 256)), dim3(256), 0, (hipStream_t)stream, pa);
+        return launch_status();
+    });
 }
 
 __attribute__((visibility("default"))) int glabc_propose_redraw(const glabc_dist* local, const glabc_chains* chains,

@@ -4,6 +4,7 @@
 
 #include <cstring>
 
+#include "glabc_pack.h"
 #include "glabc_sampler.h"
 
 namespace glabc {
@@ -27,6 +28,31 @@ inline MixArgs<D> pack_mixture(const glabc_mixture* g)
         }
     }
     return o;
+}
+
+// a DiagGaussian placeholder in StepArgs.global: the mixture variant never reads it (its kind only says that a global
+// candidate's proposal draws are normals)
+inline glabc_dist placeholder_global(int dim)
+{
+    glabc_dist g;
+    std::memset(&g, 0, sizeof g);
+    g.kind = GLABC_DIST_DIAG_GAUSS;
+    g.dim = dim;
+    for (int j = 0; j < GLABC_MAX_DIM; ++j) g.p2[j] = 1.0f;
+    return g;
+}
+
+// the argument block of the mixture kernels, built-in (glabc_mix.hip) and run-time compiled (glabc_rtc.hip): one packer
+template <int D, int YD>
+inline MixStepArgs<D, YD> pack_mix_args(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
+                                        const glabc_run* r)
+{
+    const glabc_dist ph = placeholder_global(m->theta_dim);
+    MixStepArgs<D, YD> a;
+    std::memset(&a, 0, sizeof a);
+    static_cast<StepArgs<D, YD>&>(a) = pack_args_rinv<D, YD>(m, local, &ph, c, r, 0.0f);
+    a.mix = pack_mixture<D>(g);
+    return a;
 }
 
 // GLMCMC (n_batch 1..GLABC_MAX_BATCH) or GlobalMCMC at one lane per chain, default schedule; defined in glabc_mix_dim.hip

@@ -71,30 +71,6 @@ __global__ void __launch_bounds__(256) mixture_forward_kernel(const MixRowArgs<D
 
 using namespace glabc;
 
-// a DiagGaussian placeholder in StepArgs.global: the mixture variant never reads it (its kind only says that a global
-// candidate's proposal draws are normals)
-static glabc_dist placeholder_global(int dim)
-{
-    glabc_dist g;
-    std::memset(&g, 0, sizeof g);
-    g.kind = GLABC_DIST_DIAG_GAUSS;
-    g.dim = dim;
-    for (int j = 0; j < GLABC_MAX_DIM; ++j) g.p2[j] = 1.0f;
-    return g;
-}
-
-template <int D, int YD>
-static MixStepArgs<D, YD> pack_mix_args(const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
-                                        const glabc_run* r)
-{
-    const glabc_dist ph = placeholder_global(m->theta_dim);
-    MixStepArgs<D, YD> a;
-    std::memset(&a, 0, sizeof a);
-    static_cast<StepArgs<D, YD>&>(a) = pack_args_rinv<D, YD>(m, local, &ph, c, r, 0.0f);
-    a.mix = pack_mixture<D>(g);
-    return a;
-}
-
 static int run_mix_sampler(int algo, const glabc_model* m, const glabc_dist* local, const glabc_mixture* g, const glabc_chains* c,
                            const glabc_run* r, void* stream)
 {

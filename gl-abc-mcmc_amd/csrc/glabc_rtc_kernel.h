@@ -19,13 +19,28 @@
 // GLABC_RTC_WITH_GAMMA (glabc_rtc_compile_ex / glabc_rtc_compile_wide_ex with the flag GLABC_RTC_GAMMA) adds the kernels of a Gamma prior /
 // importance / global proposal: sampler_kernel<.., VAR_GAMMA> at one lane per chain whatever GLABC_RTC_L is, its teams of three /
 // two wavefronts (GLABC_RTC_GAMMA_TEAM3 / _TEAM2, GLMCMC) and wide_kernel<.., true>.  Such a program holds no VAR_GAUSS_UNIT kernels.
+//
+// GLABC_RTC_WITH_MIX (glabc_rtc_compile_mix / glabc_rtc_compile_wide_mix) instantiates the GaussianMixture variant INSTEAD of the kernels
+// above: sampler_kernel<.., 1, VAR_MIX, 0> (one lane per chain whatever GLABC_RTC_L is: chain_step asserts it), or, with
+// GLABC_RTC_WIDE, wide_kernel<.., false, true> at the four lane counts.  Their argument block is a MixStepArgs (glabc_device.h).
 #pragma once
 
 #include "glabc_sampler.h"
 
 namespace glabc {
 
-#ifdef GLABC_RTC_WIDE
+#if defined(GLABC_RTC_WIDE) && defined(GLABC_RTC_WITH_MIX)
+}  // namespace glabc
+#include "glabc_wide.h"
+namespace glabc {
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 8, false, true>(const MixStepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 16, false, true>(const MixStepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 32, false, true>(const MixStepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+template __global__ void wide_kernel<GLABC_RTC_D, GLABC_RTC_YD, 64, false, true>(const MixStepArgs<GLABC_RTC_D, GLABC_RTC_YD>, const int);
+#elif defined(GLABC_RTC_WITH_MIX)
+template __global__ void sampler_kernel<GLABC_RTC_ALGO, GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_N, 1, VAR_MIX, 0>(
+    const MixStepArgs<GLABC_RTC_D, GLABC_RTC_YD>);
+#elif defined(GLABC_RTC_WIDE)
 }  // namespace glabc
 #include "glabc_wide.h"
 namespace glabc {

@@ -20,7 +20,8 @@ shape; batch_size <= 4096) run in the fused kernels (above 16 proposals lane gro
 ``distribution.Gamma`` prior or importance proposal is fused on the |theta| + noise Model up to theta_dim 4, on g-and-k
 (``GK_set(prior=...)``) and on a ``CompiledModel`` (its programs are then compiled with the Gamma kernels); a Gamma local increment
 is a callback and runs split-phase.  A ``distribution.GaussianMixture`` importance proposal (up to 8 modes) is fused on the
-|theta| + noise Model up to theta_dim 4 and on g-and-k with a DiagGaussian / Uniform prior, at every batch_size up to 4096 (up to 16
+|theta| + noise Model up to theta_dim 4, on g-and-k and on a ``CompiledModel`` of any theta_dim (its mixture programs, ``glabc_rtc_mix_steps``)
+with a DiagGaussian / Uniform prior, at every batch_size up to 4096 (up to 16
 proposals ``glabc_glmcmc_mix_steps``, above ``glabc_glmcmc_mix_wide_steps``, the lane-group kernel's mixture variant): ``"auto"`` then
 draws it from the kernel's Philox stream instead of torch's generator (the same law); ``path="generic"`` keeps the callback.  A
 ``compiled.CompiledModel`` (a user's simulator compiled into those kernels at run time) runs fused as well: up to 16 proposals in a register kernel
@@ -30,7 +31,8 @@ to it with a warning where that kernel fails to compile or fails its self-check.
 (``generate_samples / prior_log_prob / calculate_log_kernel``, examples/Mixture.py:5-53), any theta_dim, any batch_size
 and any proposal object run through the split-phase path of ``generic.py`` (``glabc_propose`` -> callbacks ->
 ``glabc_select``).  ``path="generic"`` forces the latter; ``path="fused"`` raises instead of falling back.
-Generic-path extras: ``callback_device`` ('auto' | 'cuda' | 'cpu'), ``sentinel_redraw`` (GLMCMC.py:92-93, default on).  A call
+Generic-path extras: ``callback_device`` ('auto' | 'cuda' | 'cpu'), ``sentinel_redraw`` (GLMCMC.py:92-93, default on),
+``kernel_stream`` (default off; on: a GaussianMixture's candidates come from ``glabc_propose_mix``, the fused kernels' draws).  A call
 that ``"auto"`` sends to a fused kernel does not take them (TypeError) -- a CompiledModel without a user prior at 17..4096
 proposals included, which ran split-phase before the lane-group kernel took such Models: pass ``path="generic"`` with them.
 """
@@ -75,8 +77,8 @@ def GLMCMC(ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal,
     local = Local_Proposal.descriptor()
     imp = Importance_Proposal.descriptor()
     mix = isinstance(imp, _capi.Mixture)                           # a GaussianMixture: the kernels' mixture variant (include/glabc.h)
-    if mix and (fast_math or model.sim_kind == _capi.SIM_USER):
-        raise ValueError("a GaussianMixture importance proposal runs fused without fast_math and on the built-in Models only")
+    if mix and fast_math:
+        raise ValueError("a GaussianMixture importance proposal runs fused without fast_math")
     dev, chains, single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
     hist = _host.allocate_history(num_ite, chains, record_history)
     mirror = _host.HostMirror(hist) if _host.HostMirror.wanted(hist, single, return_device) else None   # rows leave for the host while the kernels run

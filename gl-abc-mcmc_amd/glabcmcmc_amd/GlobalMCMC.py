@@ -2,7 +2,7 @@
 (reference: GlobalMCMC.py:6-98).  Same positional signature; the loop body
 (GlobalMCMC.py:37-68) is the fused gfx950 kernel behind ``glabc_globalmcmc_steps``.
 Shapes, return value, keyword-only extras and the fused / generic dispatch (``path``) as in ``GLMCMC``, a
-``distribution.GaussianMixture`` global proposal included."""
+``distribution.GaussianMixture`` global proposal included (on a ``CompiledModel`` too: its mixture program)."""
 from . import _capi, _host, engine, generic
 
 
@@ -28,8 +28,6 @@ def GlobalMCMC(ABCset, num_ite, Initial_theta, Initial_y,
     local = Local_Proposal.descriptor()
     glob = Global_Proposal.descriptor()
     mix = isinstance(glob, _capi.Mixture)                          # a GaussianMixture: the kernels' mixture variant (include/glabc.h)
-    if mix and model.sim_kind == _capi.SIM_USER:
-        raise ValueError("a GaussianMixture global proposal runs fused on the built-in Models only")
     dev, chains, single = _host.prepare(ABCset, Initial_theta, Initial_y, device, chain0)
     hist = _host.allocate_history(num_ite, chains, record_history)
     mirror = _host.HostMirror(hist) if _host.HostMirror.wanted(hist, single, return_device) else None   # rows leave for the host while the kernels run

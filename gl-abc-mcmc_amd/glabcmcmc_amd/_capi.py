@@ -296,6 +296,7 @@ ENTRY_POINTS = {
     "glabc_rtc_hooks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_rtc_model_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_propose": (C.c_int, [C.c_int, _P(Dist), _P(Dist), _P(Chains), _P(Run), _P(StepIO), C.c_void_p]),
+    "glabc_propose_mix": (C.c_int, [C.c_int, _P(Dist), _P(Mixture), _P(Chains), _P(Run), _P(StepIO), C.c_void_p]),
     "glabc_propose_redraw": (C.c_int, [_P(Dist), _P(Chains), _P(Run), _P(StepIO), C.c_int32, C.c_void_p, C.c_void_p]),
     "glabc_select": (C.c_int, [C.c_int, _P(Dist), _P(Chains), _P(Run), _P(StepIO), C.c_void_p]),
     "glabc_model_simulate": (C.c_int, [_P(Model), C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
@@ -310,6 +311,10 @@ ENTRY_POINTS = {
     "glabc_glmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_globalmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_glmcmc_mix_wide_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
+    "glabc_rtc_compile_mix": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p,
+                                        C.c_int64]),
+    "glabc_rtc_compile_wide_mix": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),
+    "glabc_rtc_mix_steps": (C.c_int, [C.c_void_p, _P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_model_prior_log_prob": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_model_discrepancy": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "glabc_model_log_kernel": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

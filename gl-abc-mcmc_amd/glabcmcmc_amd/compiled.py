@@ -43,6 +43,11 @@ A ``distribution.Gamma`` as the Model's prior and / or as the importance / globa
 a program compiled with ``GLABC_RTC_GAMMA`` (``program(..., gamma=True)``, a program of its own in the cache), which holds the
 Gamma kernels next to the generic ones, and its self-check runs them -- with the caller's proposal, positive start states.
 
+A ``distribution.GaussianMixture`` as the importance / global proposal runs fused as well, at any ``theta_dim``: the samplers ask for
+a mixture program (``program(..., mixture=True)``: ``glabc_rtc_compile_mix`` up to 16 proposals, ``glabc_rtc_compile_wide_mix`` once per
+Model above), launched by ``glabc_rtc_mix_steps``.  Its self-check runs it against ``glabc_propose_mix`` -> the compiled row callbacks
+-> ``glabc_select`` on the same Philox streams, with the caller's mixture.
+
 Use + - * / fmaf sqrtf fabsf and the ``glabc_*`` functions of include/glabc_numerics.h (``glabc_expf``,
 ``glabc_logf``, ``glabc_sincos2pi`` ...) for results that a CPU build of the same source reproduces bit for bit.
 """
@@ -89,9 +94,16 @@ class CompiledModel:
 
     GAMMA = "gamma"
 
-    def program(self, algo, batch_size=1, gamma=False, proposal=None):
+    MIXTURE = "mixture"
+
+    def program(self, algo, batch_size=1, gamma=False, proposal=None, mixture=False):
         """gamma: the program with the Gamma kernels (GLABC_RTC_GAMMA) -- what a sampler asks for when the prior or its importance /
-        global proposal (`proposal`: the object, for the self-check) is a Gamma.  A Model whose prior is a Gamma has no other."""
+        global proposal (`proposal`: the object, for the self-check) is a Gamma.  A Model whose prior is a Gamma has no other.
+        mixture: the program of the kernels' GaussianMixture variant (glabc_rtc_compile_mix / glabc_rtc_compile_wide_mix), launched by
+        glabc_rtc_mix_steps -- what a sampler asks for when its importance / global proposal is a GaussianMixture.  Programs of their
+        own in the cache, the wide one compiled once per Model; a Gamma prior has none (ValueError)."""
+        if mixture:
+            return self._mixture_program(int(algo), batch_size, proposal)
         algo = int(algo)
         n = 1 if algo == _capi.ALGO_GLOBALMCMC else int(batch_size)
         wide = algo == _capi.ALGO_GLMCMC and n > _capi.MAX_BATCH
@@ -141,6 +153,86 @@ class CompiledModel:
                     self._failed[key] = str(exc)
                 raise
         return self._programs[key]
+
+    def _mixture_program(self, algo, batch_size, proposal=None):
+        n = 1 if algo == _capi.ALGO_GLOBALMCMC else int(batch_size)
+        wide = algo == _capi.ALGO_GLMCMC and n > _capi.MAX_BATCH
+        if wide and n > _capi.MAX_BATCH_WIDE:
+            raise ValueError("batch_size %d: the fused kernels take 1..%d" % (n, _capi.MAX_BATCH_WIDE))
+        if self._gamma_prior():
+            raise ValueError("the mixture variant knows no Gamma prior")
+        key = (algo, self.WIDE if wide else n, self.MIXTURE)
+        if key in self._failed:
+            raise SimulatorSelfCheckError(self._failed[key])
+        if key not in self._programs:
+            handle = C.c_void_p()
+            log = C.create_string_buffer(1 << 16)
+            src = self.simulator_source.encode()
+            if wide:
+                name = "glabc_rtc_compile_wide_mix"
+                rc = _capi.lib().glabc_rtc_compile_wide_mix(src, self.theta_dim, self.y_dim, self.noise_dim, C.byref(handle), log, len(log))
+            else:
+                name = "glabc_rtc_compile_mix"
+                rc = _capi.lib().glabc_rtc_compile_mix(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, C.byref(handle), log,
+                                                       len(log))
+            if rc != _capi.OK:
+                raise SimulatorCompileError("%s failed (status %d):\n%s" % (name, rc, log.value.decode(errors="replace")))
+            self._programs[key] = handle
+        check = (algo, n, self.MIXTURE)                  # the self-check: once per batch size, as for the other programs
+        if check not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
+            self._checked.add(check)                     # before the check: it re-enters program() through the samplers
+            try:
+                self.self_check_mixture(algo, n, proposal)
+            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
+                self._checked.discard(check)
+                if wide:
+                    self._checked -= {k for k in self._checked if k[0] == algo and k[-1] == self.MIXTURE and k[1] > _capi.MAX_BATCH}
+                handle = self._programs.pop(key, None)
+                if handle is not None:
+                    _capi.lib().glabc_rtc_release(handle)
+                if isinstance(exc, SimulatorSelfCheckError):
+                    self._failed[key] = str(exc)
+                raise
+        return self._programs[key]
+
+    def self_check_mixture(self, algo, batch_size=1, proposal=None, n_chains=512, steps=4, seed=20240229):
+        """self_check for a mixture program: glabc_rtc_mix_steps against the split-phase iteration glabc_propose_mix -> this Model's
+        compiled row callbacks -> glabc_select on the same Philox streams (path="generic", kernel_stream=True), bit for bit, with the
+        caller's mixture (`proposal`), else three modes around the prior's location."""
+        from .GlobalMCMC import GlobalMCMC
+        from .GLMCMC import GLMCMC
+        dev = engine.require_device(None)
+        g = torch.Generator().manual_seed(seed)
+        d = self.theta_dim
+        pd = self.prior.descriptor()
+        loc = torch.tensor([pd.p0[j] for j in range(d)], dtype=torch.float64)
+        scale = torch.tensor([pd.p2[j] for j in range(d)], dtype=torch.float64)
+        if pd.kind == _capi.DIST_UNIFORM:                             # p0 = low, p2 = high - low
+            loc, scale = loc + 0.5 * scale, scale / 4.0
+        mix = proposal
+        if mix is None:
+            shift = torch.tensor([-1.0, 0.0, 1.0], dtype=torch.float64).view(3, 1)
+            mix = distribution.GaussianMixture(3, d, loc=(loc.view(1, d) + shift * scale.view(1, d)).numpy(),
+                                               scale=(0.6 * scale).view(1, d).expand(3, d).numpy(), weights=[1.0, 2.0, 1.0])
+        theta0 = (loc + scale * torch.randn(n_chains, d, generator=g, dtype=torch.float64)).to(torch.float32)
+        local = distribution.DiagGaussian(d, torch.zeros(d), torch.log(0.3 * scale.to(torch.float32)))
+        y0 = self.simulate_from_noise(theta0, torch.randn(n_chains, self.noise_dim, generator=g)).cpu()
+        out = []
+        for path, kw in (("fused", {}), ("generic", dict(sentinel_redraw=False, graph=False, kernel_stream=True))):
+            if algo == _capi.ALGO_GLMCMC:
+                r = GLMCMC(self, steps + 1, theta0, y0, local, None, 0.5, mix, batch_size, seed=seed, device=dev, verbose=False,
+                           path=path, **kw)
+            else:
+                r = GlobalMCMC(self, steps + 1, theta0, y0, mix, None, 0.5, local, seed=seed, device=dev, verbose=False, path=path,
+                               **kw)
+            out.append(r.contiguous().view(torch.int32))
+        if not torch.equal(out[0], out[1]):
+            bad = int((out[0] != out[1]).any(dim=-1).any(dim=0).sum()) if out[0].dim() == 3 else -1
+            raise SimulatorSelfCheckError(
+                "the run-time compiled mixture kernel (algorithm %d, batch size %d) disagrees with the split-phase path on %d of %d "
+                "chains after %d iterations: refusing to sample with it (use path='generic', and please report the "
+                "simulator source)" % (algo, batch_size, bad, n_chains, steps))
+        return True
 
     def _gamma_prior(self):
         try:

@@ -143,7 +143,8 @@ def run_steps(entry, model_desc, local_desc, global_desc, chains, n_steps, step0
     force the launch geometry (results are identical for every choice).
     gf_per_chain: None or float32 device tensor [C] replacing global_frequency chain by chain.
     rtc_program: handle of glabc_rtc_compile -- the launches then go to glabc_rtc_steps (a Model whose simulator was compiled
-    into the kernel at run time, compiled.CompiledModel) with the same arguments.
+    into the kernel at run time, compiled.CompiledModel) with the same arguments; with a _capi.Mixture global_desc the handle is a
+    mixture program's (glabc_rtc_compile_mix / _wide_mix) and the launches go to glabc_rtc_mix_steps.
     math_mode: _capi.MATH_EXACT (default: the specified arithmetic, reproduced bit for bit by the CPU checker) or _capi.MATH_FAST
     (glabc_glmcmc_steps only, opt-in: hardware transcendentals -- the same law from another stream of normals, include/glabc.h).
     dump_draws: MATH_FAST only -- (u [C][n_steps][2] float32, r [C][n_steps] float64, z [C][n_steps][N][d + y_dim] float32) device
@@ -152,11 +153,12 @@ def run_steps(entry, model_desc, local_desc, global_desc, chains, n_steps, step0
     memory on a second stream while the next launch runs (launches are then cut to mirror.steps_per_launch rows).
     """
     lib = _capi.lib()
-    if rtc_program is not None:
-        entry = "glabc_rtc_steps"
+    if rtc_program is not None:                                    # a mixture program (CompiledModel.program(mixture=True)) has its own entry point
+        entry = "glabc_rtc_mix_steps" if isinstance(global_desc, _capi.Mixture) else "glabc_rtc_steps"
+        rtc_fn = getattr(lib, entry)
 
         def fn(*a):
-            return lib.glabc_rtc_steps(rtc_program, *a)
+            return rtc_fn(rtc_program, *a)
     else:
         fn = getattr(lib, entry)
     k_max = int(steps_per_launch or MAX_STEPS_PER_LAUNCH)

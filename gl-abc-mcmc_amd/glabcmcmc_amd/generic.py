@@ -66,8 +66,11 @@ def dist_descriptor(obj, dim, gamma=False):
 
 def rtc_program(ABCset, model_desc, proposal, algo, batch_size=1):
     """a CompiledModel's program for a sampler call: the one with the Gamma kernels (GLABC_RTC_GAMMA) when the Model's prior or the
-    importance / global proposal is a Gamma, checked with the caller's proposal"""
+    importance / global proposal is a Gamma, checked with the caller's proposal; the mixture program (glabc_rtc_compile_mix /
+    _wide_mix, launched by glabc_rtc_mix_steps) when that proposal is a GaussianMixture"""
     d = try_descriptor(proposal)
+    if isinstance(d, _capi.Mixture):
+        return ABCset.program(algo, batch_size, mixture=True, proposal=proposal)
     if model_desc.prior.kind == _capi.DIST_GAMMA or (isinstance(d, _capi.Dist) and d.kind == _capi.DIST_GAMMA):
         return ABCset.program(algo, batch_size, gamma=True, proposal=proposal)
     return ABCset.program(algo, batch_size)
@@ -80,7 +83,9 @@ def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, ga
     programs are then compiled with GLABC_RTC_GAMMA (include/glabc.h).
     mixture_ok: the caller has the mixture entry points (glabc_glmcmc_mix_steps / glabc_globalmcmc_mix_steps): a
     distribution.GaussianMixture (a _capi.Mixture descriptor) as the LAST proposal, on the |theta| + noise Model up to theta_dim 4
-    and on g-and-k, batch sizes up to GLABC_MAX_BATCH, no Gamma prior; anywhere else a mixture stays a callback.
+    and on g-and-k, and on a compiled.CompiledModel at any theta_dim (its mixture programs, glabc_rtc_mix_steps; with a user prior up
+    to GLABC_MAX_BATCH proposals only, as for Gaussian proposals), batch sizes up to GLABC_MAX_BATCH, no Gamma prior; anywhere else a
+    mixture stays a callback.
     mixture_max_batch: the largest batch size the caller's mixture entry points take, where that is more than GLABC_MAX_BATCH (GLMCMC:
     glabc_glmcmc_mix_wide_steps, GLABC_MAX_BATCH_WIDE); the rest of the mixture's matrix is the same."""
     m = try_descriptor(ABCset)
@@ -90,8 +95,11 @@ def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, ga
     for i, p in enumerate(proposals):
         d = try_descriptor(p)
         if isinstance(d, _capi.Mixture):
+            # a compiled.CompiledModel: its mixture programs, any theta_dim; a user prior above GLABC_MAX_BATCH stays split-phase as below
+            user = (m.sim_kind == _capi.SIM_USER and hasattr(ABCset, "program") and
+                    (batch_size is None or int(batch_size) <= _capi.MAX_BATCH or not getattr(ABCset, "user_prior", False)))
             return bool(mixture_ok and i == len(proposals) - 1 and i > 0 and d.dim == m.theta_dim and not gamma and
-                        ((m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4) or m.sim_kind == _capi.SIM_GK) and
+                        ((m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4) or m.sim_kind == _capi.SIM_GK or user) and
                         (batch_size is None or 1 <= int(batch_size) <= (mixture_max_batch or _capi.MAX_BATCH)))
         if d is None or not isinstance(d, _capi.Dist) or d.dim != m.theta_dim:
             return False
@@ -256,14 +264,24 @@ class SplitPhase:
             run_.moments = C.pointer(self._moments)
         self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)      # of the construction; a capture passes its own
         self.held = ()                                                             # tensors whose addresses the StepIO holds
+        self.q_cur = None                                                          # glabc_propose_mix's, made at its first call
 
     def at(self, i):
         """the next launches are iteration i: its Philox index and its row of the history"""
         self.run_.step0 = i
         self.run_.history = self._hist_ptr + i * self._hist_row_bytes if self.hist is not None else None
 
-    def propose(self, algo, local_desc, global_desc, stream=None):
-        """glabc_propose: every random draw of the iteration, and the candidates of the proposals that have a descriptor"""
+    def propose(self, algo, local_desc, global_desc, stream=None, mixture=None):
+        """glabc_propose: every random draw of the iteration, and the candidates of the proposals that have a descriptor.
+        mixture: a _capi.Mixture -- glabc_propose_mix instead: the global candidates and their log q from the mixture on the kernel's
+        Philox stream, and q_cur (a buffer of the working set, which glabc_select then reads) for every chain"""
+        if mixture is not None:
+            if self.q_cur is None:
+                self.q_cur = torch.zeros(self.n, dtype=torch.float32, device=self.dev)
+                self.io.q_cur = self.q_cur.data_ptr()
+            _capi.check(self.lib.glabc_propose_mix(algo, _ref(local_desc), C.byref(mixture), C.byref(self.cs), C.byref(self.run_),
+                                                   C.byref(self.io), self.stream if stream is None else stream), "glabc_propose_mix")
+            return
         _capi.check(self.lib.glabc_propose(algo, _ref(local_desc), _ref(global_desc), C.byref(self.cs), C.byref(self.run_),
                                            C.byref(self.io), self.stream if stream is None else stream), "glabc_propose")
 
@@ -287,12 +305,18 @@ class Iteration:
     """One iteration of GLMCMC or GlobalMCMC for all chains of a SplitPhase: glabc_propose, the callback proposals, the Model's
     prior with the sentinel redraw of GLMCMC.py:92-93, simulate / kernel, glabc_select."""
 
-    def __init__(self, sp, algo, Local_Proposal, Global_Proposal, sentinel_redraw, max_redraws):
+    def __init__(self, sp, algo, Local_Proposal, Global_Proposal, sentinel_redraw, max_redraws, kernel_stream=False):
         self.sp, self.algo, self.max_redraws = sp, algo, max_redraws
         self.local_desc = dist_descriptor(Local_Proposal, sp.d) if Local_Proposal is not None else None
         self.global_desc = dist_descriptor(Global_Proposal, sp.d, gamma=True)
+        # kernel_stream: a GaussianMixture global proposal is drawn and scored by glabc_propose_mix, not by its callback
+        self.mix_desc = try_descriptor(Global_Proposal) if kernel_stream else None
+        if not isinstance(self.mix_desc, _capi.Mixture):
+            self.mix_desc = None
+        elif self.mix_desc.dim != sp.d:
+            raise ValueError("proposal dimension %d does not match Model.theta_dim = %d" % (self.mix_desc.dim, sp.d))
         self.local_cb = ProposalCallbacks(Local_Proposal, sp.dev) if (self.local_desc is None and Local_Proposal is not None) else None
-        self.global_cb = ProposalCallbacks(Global_Proposal, sp.dev) if self.global_desc is None else None
+        self.global_cb = ProposalCallbacks(Global_Proposal, sp.dev) if (self.global_desc is None and self.mix_desc is None) else None
         self.redraw = sentinel_redraw and algo == _capi.ALGO_GLMCMC
         self.n_redrawn = torch.zeros(1, dtype=torch.int32, device=sp.dev)
         self.col_index = torch.arange(sp.n, device=sp.dev).view(1, sp.n)
@@ -308,7 +332,7 @@ class Iteration:
         stream = C.c_void_p(torch.cuda.current_stream(sp.dev).cuda_stream)
         if i is not None:
             sp.at(i)
-        sp.propose(self.algo, self.local_desc, self.global_desc, stream)
+        sp.propose(self.algo, self.local_desc, self.global_desc, stream, mixture=self.mix_desc)
         if self.global_cb is not None or self.local_cb is not None:
             self.callback_proposals()
         prior_prop = sp.model.prior(sp.theta_prop)                     # GLMCMC.py:74,92,96
@@ -322,7 +346,7 @@ class Iteration:
             raise ValueError("generate_samples returned %d columns, Initial_y has %d" % (y_prop.shape[1], sp.yd))
         kern_prop = sp.model.kernel(y_prop)                            # GLMCMC.py:72,96
         # Importance_Proposal.log_prob(Theta_old), GLMCMC.py:63
-        q_cur = self.global_cb.log_prob(sp.chains.theta.t().contiguous()) if self.global_cb is not None else None
+        q_cur = self.global_cb.log_prob(sp.chains.theta.t().contiguous()) if self.global_cb is not None else sp.q_cur
         sp.select(self.algo, self.global_desc, prior_prop, y_prop, kern_prop, q_cur, stream)
 
     def callback_proposals(self):
@@ -442,7 +466,7 @@ def _copy_all(dst, src):
 def run(algo, ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Global_Proposal, filelocation, global_frequency,
         batch_size, csv_variant, *, seed=None, device=None, chain0=0, record_history=True, stats=None, return_device=False,
         verbose=True, state_out=None, callback_device="auto", sentinel_redraw=True, max_redraws=100000, max_graph_rounds=32,
-        progress=None, graph="auto"):
+        progress=None, graph="auto", kernel_stream=False):
     """GLMCMC (algo = _capi.ALGO_GLMCMC, GLMCMC.py:24-137) or GlobalMCMC (_capi.ALGO_GLOBALMCMC, GlobalMCMC.py:6-98) with
     the Model -- and, if need be, the proposals -- as callbacks.  Same return value and side effects as the fused path.
 
@@ -452,13 +476,17 @@ def run(algo, ABCset, num_ite, Initial_theta, Initial_y, Local_Proposal, Global_
     replayed; 'auto' falls back to launching eagerly when the capture is not possible (e.g. a callback that synchronises).
     With the sentinel check on (GLMCMC's default) the replay is speculative, see replay_segments: same results as the eager
     loop; a prior that does return the sentinel keeps the run a replayed graph, with up to max_graph_rounds redraw rounds
-    inside it."""
+    inside it.
+
+    kernel_stream: False (default) | True.  With a GaussianMixture as Global_Proposal, True takes its candidates and q(Theta_old) from
+    glabc_propose_mix -- the kernel's Philox stream, the draws of the fused mixture kernels, bit for bit -- instead of the object's
+    forward / log_prob callbacks (torch's generator; the same law).  Other proposals are not affected."""
     N = int(batch_size) if algo == _capi.ALGO_GLMCMC else 1
     if N < 1:
         raise ValueError("batch_size must be >= 1")
     sp = SplitPhase(ABCset, num_ite, Initial_theta, Initial_y, device, chain0, seed, N, global_frequency, callback_device,
                     record_history, stats)
-    step = Iteration(sp, algo, Local_Proposal, Global_Proposal, sentinel_redraw, max_redraws)
+    step = Iteration(sp, algo, Local_Proposal, Global_Proposal, sentinel_redraw, max_redraws, kernel_stream)
     if Local_Proposal is None and float(global_frequency) < 1:
         raise ValueError("a local proposal is needed unless global_frequency >= 1")
     dev, chains = sp.dev, sp.chains

@@ -582,6 +582,8 @@ int glabc_gamma_forward(const glabc_gamma* dist, int64_t n, uint64_t seed, int64
  *   z_q = eps_q * scale[k][q] + loc[k][q] (two roundings), theta'_q = (float) z_q, log q' = (float) log_prob(z) -- the density
  *   of the DOUBLE variate, as for Gamma.  log_prob of a float32 state is (float) log_prob((double) theta).
  * Existing draws are untouched (GLABC_STREAM_LAYOUT stays 2).
+ * On a GLABC_SIM_USER Model the same kernels are compiled around the user's source at run time, for theta_dim 1..8 and any y_dim /
+ * noise_dim (glabc_rtc_compile_mix / glabc_rtc_compile_wide_mix / glabc_rtc_mix_steps, below).
  * Where the fused samplers take it (glabc_glmcmc_mix_steps / glabc_globalmcmc_mix_steps / glabc_init_weights_mix): GLABC_SIM_ABS_GAUSS
  * with theta_dim 1..4 and GLABC_SIM_GK, batch size 1..GLABC_MAX_BATCH, prior and local increment DiagGaussian or Uniform, with
  * history, moments, global_frequency_per_chain and GLABC_DEBUG_EXACT_INDEX; one lane per chain in the default schedule
@@ -624,6 +626,41 @@ int glabc_globalmcmc_mix_steps(const glabc_model* model, const glabc_dist* local
                                const glabc_chains* chains, const glabc_run* run, void* stream);
 int glabc_glmcmc_mix_wide_steps(const glabc_model* model, const glabc_dist* local, const glabc_mixture* importance,
                                 const glabc_chains* chains, const glabc_run* run, void* stream);
+
+/* The mixture variant around a USER simulator (GLABC_SIM_USER): glabc_rtc_compile / glabc_rtc_compile_wide with the kernels of the
+ * three entry points above instead of the generic ones -- sampler_kernel<.., VAR_MIX> at one lane per chain for one (algorithm,
+ * batch size 1..GLABC_MAX_BATCH), or the lane-group kernel's mixture variant at 8 / 16 / 32 / 64 lanes per chain for any batch size
+ * GLABC_MAX_BATCH + 1..GLABC_MAX_BATCH_WIDE -- for theta_dim, y_dim and noise_dim 1..GLABC_MAX_DIM each, user hooks included.  New entry
+ * points, not a `flags` bit of the _ex calls.  Register or scratch spills of a kernel are named in `log` (slower, never wrong).
+ * glabc_rtc_simulate / glabc_rtc_hooks / glabc_rtc_model_rows / glabc_rtc_release take such a program unchanged; glabc_rtc_steps
+ * refuses it (GLABC_ERR_KIND), as glabc_rtc_mix_steps refuses a program of the other kind.
+ * glabc_rtc_mix_steps names its kernel itself (no launch plan): a register program takes its compiled batch size at lanes_per_chain
+ * 0 or 1, a wide program 17..4096 at lanes_per_chain 0 (wide_default_lanes) or 8 / 16 / 32 / 64.  Checks, first defect wins: a null
+ * pointer (GLABC_ERR_NULL); sim_kind != GLABC_SIM_USER (GLABC_ERR_KIND); theta_dim / y_dim / noise.dim other than the program's
+ * (GLABC_ERR_DIM); a program not compiled by the two calls below (GLABC_ERR_KIND); a Gamma prior (GLABC_ERR_KIND); an invalid prior,
+ * local increment or kernel scale (GLABC_ERR_ARG); a tape, GLABC_MATH_FAST or dump_draws (GLABC_ERR_ARG); the mixture's own checks as
+ * glabc_glmcmc_mix_steps makes them; the chains; n_steps < 0, step0_device, batch size and lanes_per_chain (GLABC_ERR_ARG);
+ * global_frequency, history, moments and the step counter as every stepping entry point.  Then, for a wide program, group rows
+ * that with the kernel's static LDS exceed what the device gives a workgroup: GLABC_ERR_ARG, before anything runs.  The chains start
+ * as for glabc_rtc_steps (GLABC_FLAG_LOCAL set: log_w is computed at the first global move), so there is no init-weights twin. */
+/* glabc_propose(algo, local, NULL, ...) with the rows it leaves to the caller filled from a GaussianMixture, in the same launch: the
+ * split-phase twin of the mixture kernels, drawing from the kernel's Philox stream.  Head draws, is_global, the local move's row and
+ * every candidate's sim_noise are glabc_propose's.  On top: theta_prop and log_q of every row j > 0, and of row 0 for chains whose
+ * is_global bit 0 is set, are what the fused kernels compute (above: mode uniform at GLABC_SLOT_MIX + j, the candidate's proposal
+ * normals promoted to double, z = eps * scale + loc, theta' = (float) z, log q' = (float) log_prob(z)); and io->q_cur[c] =
+ * (float) log_prob((double) Theta_old) is WRITTEN for every chain, for glabc_select(algo, NULL, ...) to read.  algo GLABC_ALGO_GLMCMC /
+ * GLABC_ALGO_GLOBALMCMC (else GLABC_ERR_KIND), theta_dim 1..8 (GLABC_ERR_DIM), then the mixture's checks as glabc_glmcmc_mix_steps makes
+ * them (the mixture against io->theta_dim, the local increment -- which may be NULL as for glabc_propose --, null chains / run, a
+ * tape), a null io->q_cur (GLABC_ERR_NULL), then glabc_propose's own checks. */
+int glabc_propose_mix(int algo, const glabc_dist* local, const glabc_mixture* global, const glabc_chains* chains,
+                      const glabc_run* run, const glabc_step_io* io, void* stream);
+
+int glabc_rtc_compile_mix(const char* simulator_source, int32_t algo, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
+                          int32_t batch_size, glabc_rtc_program** out, char* log, int64_t log_size);
+int glabc_rtc_compile_wide_mix(const char* simulator_source, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
+                               glabc_rtc_program** out, char* log, int64_t log_size);
+int glabc_rtc_mix_steps(const glabc_rtc_program* program, const glabc_model* model, const glabc_dist* local,
+                        const glabc_mixture* global, const glabc_chains* chains, const glabc_run* run, void* stream);
 
 /* Model callbacks on n row-major points (Mixture.py:28-45): used by the host
  * mirror's Model class and by the parity tests. */

@@ -7,7 +7,10 @@ the median and the spread (max - min) of the repeats are reported, and (a) beats
 both spreads.  --split-iters gives (b) a shorter call of its own (it is three orders of magnitude slower); the comparison is then
 one of seconds per iteration, and each entry names its own iteration count.
 
-    python tools/mixture_bench.py [--chains 65536] [--iters 2000] [--split-iters ITERS] [--batch 5] [--repeats 3]
+--compiled runs the same calls on a CompiledModel whose source is the |theta| + noise simulator: (a) is then the run-time compiled
+mixture program (glabc_rtc_mix_steps), (b) the callback path such a call took before those programs existed.
+
+    python tools/mixture_bench.py [--chains 65536] [--iters 2000] [--split-iters ITERS] [--batch 5] [--repeats 3] [--compiled]
                                   [--out profiles/mixture_bench.json]
 """
 import argparse
@@ -23,6 +26,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gl-abc-mcmc_amd"))
 import glabcmcmc_amd as g  # noqa: E402
 from glabcmcmc_amd.examples.Mixture import Mixture_set  # noqa: E402
+
+
+# examples/Mixture.py:19-23 as user source: y = |theta| + sqrt(0.05) eps
+COMPILED_SOURCE = """
+GLABC_SIMULATOR void glabc_user_simulate(const float* theta, const float* eps, float* y)
+{
+    for (int j = 0; j < GLABC_Y_DIM; ++j) y[j] = fabsf(theta[j]) + 0.2236068f * eps[j];
+}
+"""
 
 
 def clocked(fn):
@@ -41,10 +53,13 @@ def main():
     ap.add_argument("--batch", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup-iters", type=int, default=20)
+    ap.add_argument("--compiled", action="store_true", help="a CompiledModel with the |theta| + noise simulator as C source")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.cuda.set_device(0)
     model = Mixture_set(0.05)
+    if a.compiled:
+        model = g.CompiledModel(2, 2, COMPILED_SOURCE, g.DiagGaussian(2, torch.zeros(2), torch.zeros(2)), [1.5, 1.5], 0.05)
     lp = g.DiagGaussian(2, torch.zeros(1, 2), torch.log(torch.tensor([0.35, 0.35])))
     mix = g.GaussianMixture(4, 2, loc=[[1.5, 1.5], [1.5, -1.5], [-1.5, 1.5], [-1.5, -1.5]], scale=[[0.5, 0.5]] * 4)
     gauss = g.DiagGaussian(2, torch.tensor([0.0, 0.0]), torch.log(torch.tensor([1.6, 1.6])))
@@ -66,7 +81,8 @@ def main():
     for _ in range(a.repeats):                               # (a) and (b) alternate; (c) rides along
         for name in ("fused_mixture", "split_phase_mixture", "fused_diag_gaussian"):
             times[name].append(clocked(runs[name]))
-    res = {"workload": "GLMCMC on Mixture_set, theta_dim 2, 4-mode GaussianMixture importance proposal", "chains": a.chains,
+    res = {"workload": "GLMCMC on %s, theta_dim 2, 4-mode GaussianMixture importance proposal"
+                       % ("a CompiledModel (|theta| + noise as C source)" if a.compiled else "Mixture_set"), "chains": a.chains,
            "iterations": a.iters, "batch_size": a.batch, "repeats": a.repeats, "device": torch.cuda.get_device_name(0)}
     for name, ts in times.items():
         k = float(iters[name])
