@@ -182,6 +182,38 @@ inline int check_mix_wide_run(const glabc_model* m, const glabc_dist* local, con
     return check_mix_steps(m, local, g, c, r, true, true);
 }
 
+// ---- glabc_glmala_mix_steps: glabc_glmala_steps' checks in glabc_glmala_steps' order, with the mixture's own where that entry point
+// checks its importance proposal.  The order is the contract (include/glabc.h): the model (a Gamma prior is GLABC_ERR_KIND there),
+// the simulator kind, theta_dim 5..8 (GLABC_ERR_DIM: no kernel is instantiated; glabc_glmala_steps finds that out last), the mixture,
+// null mala / run, the chains, n_steps and the batch size, global_frequency, global_frequency_per_chain, the MALA parameters,
+// history, moments, tape / math mode / dump_draws, lanes_per_chain, the step counter.
+inline int check_mala_params(const glabc_mala* p)
+{
+    return (p->num_grad < 2 || p->num_grad > (1 << 16) || !(p->tau > 0.0) || !std::isfinite(p->tau) || !std::isfinite(p->tau_sq) ||
+            !std::isfinite(p->eps_sq) || !(p->eps_sq >= 0.0))
+               ? GLABC_ERR_ARG
+               : GLABC_OK;
+}
+
+inline int check_mala_mix_run(const glabc_model* m, const glabc_mixture* g, const glabc_mala* p, const glabc_chains* c, const glabc_run* r)
+{
+    if (int e = check_model(m)) return e;
+    if (m->sim_kind != GLABC_SIM_ABS_GAUSS) return GLABC_ERR_KIND;
+    if (m->theta_dim > 4) return GLABC_ERR_DIM;
+    if (int e = check_mixture(g, m->theta_dim)) return e;
+    if (!p || !r) return GLABC_ERR_NULL;
+    if (int e = check_chains(c, CHAINS_MALA)) return e;
+    if (r->n_steps < 0 || r->batch_size < 1 || r->batch_size > GLABC_MAX_BATCH) return GLABC_ERR_ARG;
+    if (int e = check_frequency(r)) return e;
+    if (r->global_frequency_per_chain) return GLABC_ERR_ARG;        // GLMCMC / GlobalMCMC only
+    if (int e = check_mala_params(p)) return e;
+    if (int e = check_history(r, c->n_chains)) return e;
+    if (int e = check_moments(r)) return e;
+    if (r->tape || r->math_mode != GLABC_MATH_EXACT || r->dump_draws) return GLABC_ERR_ARG;
+    if (r->lanes_per_chain < 0 || r->lanes_per_chain > 2) return GLABC_ERR_ARG;      // wavefronts per 64 chains (theta_dim 2)
+    return check_step_counter(r);
+}
+
 // ---- glabc_propose_mix: the mixture's checks in the order glabc_glmcmc_mix_steps makes them (the mixture, the local increment, the
 // pointers, a tape), ahead of glabc_propose's own, which the entry point makes next.  io gives the dimension the mixture must have;
 // local may be null as for glabc_propose (the caller then fills the local move's row); io->q_cur is written, so it must be there

@@ -22,6 +22,7 @@
 #include "glabc_dispatch.h"
 #include "glabc_launch.h"
 #include "glabc_mala.h"
+#include "glabc_mix.h"
 #include "glabc_pack.h"
 #include "glabc_plan.h"
 #include "glabc_sampler.h"
@@ -691,7 +692,35 @@ static MalaArgs<D> pack_mala(const glabc_model* m, const glabc_dist* imp, const 
     return a;
 }
 
+// the argument block of the mixture variant: pack_mala with a placeholder where the importance proposal stands (the variant never
+// reads it), then the mixture's compacted tables
+template <int D>
+static MalaMixArgs<D> pack_mala_mix(const glabc_model* m, const glabc_mixture* g, const glabc_mala* p, const glabc_chains* c,
+                                    const glabc_run* r, const Tuning& tune)
+{
+    const glabc_dist ph = placeholder_global(m->theta_dim);
+    MalaMixArgs<D> a;
+    std::memset(&a, 0, sizeof a);
+    a.m = pack_mala<D>(m, &ph, p, c, r, tune);
+    a.mix = pack_mixture<D>(g);
+    return a;
+}
+
 extern "C" {
+
+__attribute__((visibility("default"))) int glabc_glmala_mix_steps(const glabc_model* model, const glabc_mixture* importance,
+                                                                  const glabc_mala* mala, const glabc_chains* c,
+                                                                  const glabc_run* r, void* stream)
+{
+    if (int e = check_mala_mix_run(model, importance, mala, c, r)) return e;
+    if (c->n_chains == 0 || r->n_steps == 0) return GLABC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const Tuning tune = read_tuning();
+    return dispatch_range<1, 4>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return launch_glmala_mix_dim<D>(r->batch_size, pack_mala_mix<D>(model, importance, mala, c, r, tune), s);
+    });
+}
 
 __attribute__((visibility("default"))) int glabc_glmala_steps(const glabc_model* model, const glabc_dist* importance,
                                                               const glabc_mala* mala, const glabc_chains* c,

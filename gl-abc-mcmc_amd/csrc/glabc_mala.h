@@ -38,6 +38,47 @@ struct MalaArgs {
     int32_t prio;                // team kernel: s_setprio of the main wavefront (it carries the serial part of an iteration)
 };
 
+// The mixture variant (MX) of the kernels below: the iSIR move's importance proposal is a GaussianMixture (glabc_glmala_mix_steps,
+// include/glabc.h).  Its argument block is the MalaArgs followed by the mixture's compacted tables; m.s.global is a placeholder the
+// variant never reads.
+template <int D>
+struct MalaMixArgs {
+    MalaArgs<D> m;
+    MixArgs<D> mix;
+};
+
+template <int D, bool MX>
+struct MalaKernelArgs {
+    using type = MalaArgs<D>;
+};
+template <int D>
+struct MalaKernelArgs<D, true> {
+    using type = MalaMixArgs<D>;
+};
+
+template <int D>
+GLABC_DEV const MalaArgs<D>& mala_of(const MalaArgs<D>& m) { return m; }
+template <int D>
+GLABC_DEV const MalaArgs<D>& mala_of(const MalaMixArgs<D>& mm) { return mm.m; }
+
+// The tables of the kernel's argument, where they lie in the kernel-argument segment (mix_of, glabc_device.h: read from there a
+// run-time mode index is the offset of a scalar load; indexing the by-value copy sends the block to scratch).  The block must be
+// the kernel's FIRST argument, passed as it arrived; a kernel that takes a plain MalaArgs has nothing to hand over.
+template <int D>
+GLABC_DEV const MixArgs<D>* mala_mix_of(const MalaMixArgs<D>&)
+{
+    constexpr unsigned long OFF = (sizeof(MalaArgs<D>) + 7ul) & ~7ul;
+    static_assert(sizeof(MalaMixArgs<D>) == OFF + sizeof(MixArgs<D>), "MalaMixArgs = MalaArgs, then the tables");
+    const char* base = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+    return (const MixArgs<D>*)(base + OFF);
+}
+template <int D>
+GLABC_DEV const MixArgs<D>* mala_mix_of(const MalaArgs<D>&) { return nullptr; }
+
+// LDS floats of one wavefront's staged mixture candidates (the log weight of each), lane-interleaved
+template <int N>
+constexpr int MALA_MIX_STAGE = N * 64;
+
 // distribution.py:176-181 / 81-86 on a float64 tensor
 template <int D>
 GLABC_DEV double dist_log_prob_f64(const DistArgs<D>& g, const double (&z)[D])
@@ -507,13 +548,25 @@ GLABC_DEV void candidate_draws(const Rng& rng, uint32_t step, int j, bool unifor
     }
 }
 
-// the iSIR global move of GLMALA.py:151-180
-template <int D, int N>
-GLABC_DEV bool mala_isir_move(const MalaArgs<D>& m, const Rng& rng, uint32_t step, double u_res, MalaChain<D>& c)
+// the iSIR global move of GLMALA.py:151-180.  MX: the importance proposal is the mixture `mx` (include/glabc.h,
+// glabc_glmala_mix_steps) and `stage` this lane's column of MALA_MIX_STAGE<N> floats of LDS; else both are unused.
+template <int D, int N, bool MX = false>
+GLABC_DEV bool mala_isir_move(const MalaArgs<D>& m, const Rng& rng, uint32_t step, double u_res, MalaChain<D>& c,
+                              [[maybe_unused]] const MixArgs<D>* mx = nullptr, [[maybe_unused]] float* stage = nullptr)
 {
     const StepArgs<D>& a = m.s;
     if (c.flags & GLABC_FLAG_LOCAL) {                                                        // :152-156
-        if (c.flags & GLABC_FLAG_TH64) {
+        if constexpr (MX) {
+            // one evaluation serves both precisions: a float32 state is carried in doubles exactly, so c.theta IS (double) theta
+            const double lp = mix_log_prob<D>(*mx, c.theta);
+            if (c.flags & GLABC_FLAG_TH64) {
+                c.log_w = (state_prior<D>(a, c) + state_kernel<D>(a, c)) - lp;
+                c.flags |= GLABC_FLAG_LW64;
+            } else {
+                const float q = (float)lp;
+                c.log_w = (double)(((float)state_prior<D>(a, c) + (float)state_kernel<D>(a, c)) - q);
+            }
+        } else if (c.flags & GLABC_FLAG_TH64) {
             c.log_w = (state_prior<D>(a, c) + state_kernel<D>(a, c)) - dist_log_prob_f64<D>(a.global, c.theta);
             c.flags |= GLABC_FLAG_LW64;
         } else {
@@ -525,17 +578,35 @@ GLABC_DEV bool mala_isir_move(const MalaArgs<D>& m, const Rng& rng, uint32_t ste
         }
     }
     c.flags &= ~GLABC_FLAG_LOCAL;                                                            // :157
+    // A mixture's candidates are evaluated in a ROLLED loop, one at a time, and only their weights are kept: staged in LDS (each
+    // lane reads back only what it wrote: no barrier).  The float64 density is compiled once instead of N times, and no theta' / y'
+    // of a candidate outlives its turn -- the chosen one is drawn again below from the same Philox words (every draw is a function
+    // of (seed, chain, iteration, slot), so the second evaluation is the first bit for bit).  The registers the move needs do not
+    // grow with N.
     float th[N][D], yy[N][D], lw0[N];
     const bool uni = a.global.kind == GLABC_DIST_UNIFORM;
+    if constexpr (MX) {
+#pragma unroll 1
+        for (int j = 0; j < N; ++j) {
+            float e[D], s[D], thj[D], yj[D], lq;
+            candidate_draws<D>(rng, step, j, false, e, s);
+            dist_mix_forward<D>(*mx, rng.c0, rng.c1, rng.k0, rng.k1, step, j, e, thj, lq);
+            model_simulate<D>(a, thj, s, yj);                                                // :163
+            stage[j * 64] = (dist_log_prob<D>(a.prior, thj) + model_log_kernel<D>(a, yj)) - lq;   // :164-165
+        }
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-        float e[D], s[D];
-        candidate_draws<D>(rng, step, j, uni, e, s);
+        for (int j = 0; j < N; ++j) lw0[j] = stage[j * 64];
+    } else {
 #pragma unroll
-        for (int q = 0; q < D; ++q) th[j][q] = a.global.p0[q] + a.global.p2[q] * e[q];       // :158
-        const float lq = dist_forward_log_p<D>(a.global, e);
-        model_simulate<D>(a, th[j], s, yy[j]);                                               // :163
-        lw0[j] = (dist_log_prob<D>(a.prior, th[j]) + model_log_kernel<D>(a, yy[j])) - lq;    // :164-165
+        for (int j = 0; j < N; ++j) {
+            float e[D], s[D];
+            candidate_draws<D>(rng, step, j, uni, e, s);
+#pragma unroll
+            for (int q = 0; q < D; ++q) th[j][q] = a.global.p0[q] + a.global.p2[q] * e[q];   // :158
+            const float lq = dist_forward_log_p<D>(a.global, e);
+            model_simulate<D>(a, th[j], s, yy[j]);                                           // :163
+            lw0[j] = (dist_log_prob<D>(a.prior, th[j]) + model_log_kernel<D>(a, yy[j])) - lq;    // :164-165
+        }
     }
     int ind = -1;
     if (c.flags & GLABC_FLAG_LW64) {
@@ -568,26 +639,78 @@ GLABC_DEV bool mala_isir_move(const MalaArgs<D>& m, const Rng& rng, uint32_t ste
         }
     }
     const bool moved = ind > 0;                                                              // :175-179
+    if constexpr (MX) {
+        if (moved) {                                     // the chosen candidate again: its mode, its variate, its simulation
+            const int j = ind - 1;
+            float e[D], s[D], thj[D], yj[D];
+            candidate_draws<D>(rng, step, j, false, e, s);
+            const glabc_u32x4 w = glabc_philox4x32_10(rng.c0, rng.c1, step, GLABC_SLOT_MIX + (uint32_t)j, rng.k0, rng.k1);
+            double z[D];
+            mix_draw<D>(*mx, glabc_uniform_f64(w.v[0], w.v[1]), e, z);
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-        if (ind == j + 1) {
+            for (int q = 0; q < D; ++q) thj[q] = (float)z[q];
+            model_simulate<D>(a, thj, s, yj);
 #pragma unroll
             for (int q = 0; q < D; ++q) {
-                c.theta[q] = (double)th[j][q];
-                c.y[q] = (double)yy[j][q];
+                c.theta[q] = (double)thj[q];
+                c.y[q] = (double)yj[q];
             }
-            c.log_w = (double)lw0[j];
+            c.log_w = (double)stage[j * 64];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            if (ind == j + 1) {
+#pragma unroll
+                for (int q = 0; q < D; ++q) {
+                    c.theta[q] = (double)th[j][q];
+                    c.y[q] = (double)yy[j][q];
+                }
+                c.log_w = (double)lw0[j];
+            }
         }
     }
     return moved;
 }
 
-// At most 256 registers (amdgpu_waves_per_eu): launches of more than one wavefront per SIMD then run two per SIMD.
-template <int D, int N, bool LEAN>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) glmala_kernel(const MalaArgs<D> m)
+// The float32 constants the float64 densities promote (dist_log_prob_f64, model_log_kernel_f64), made opaque to the compiler: it
+// then promotes them where they are used.  Left alone it hoists the ~20 conversions of theta_dim 4 out of the step loop as
+// loop-invariant vector registers, and keeps them -- in scratch -- across the gradients.  No instruction is emitted.
+template <int D>
+GLABC_DEV void reread_constants(MalaArgs<D>& ml)
 {
+    auto opaque = [](float& x) { asm volatile("" : "+s"(x)); };
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        opaque(ml.s.prior.p0[j]);
+        opaque(ml.s.prior.p1[j]);
+        opaque(ml.s.prior.p2[j]);
+        opaque(ml.s.y_obs[j]);
+    }
+    opaque(ml.s.prior.c0);
+    opaque(ml.s.kern_scale);
+    opaque(ml.s.kern_log_scale);
+}
+
+// At most 256 registers (amdgpu_waves_per_eu): launches of more than one wavefront per SIMD then run two per SIMD.
+// MX: the mixture variant, whose staged candidates take LDS of their own.
+template <int D, int N, bool LEAN, bool MX = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+glmala_kernel(const typename MalaKernelArgs<D, MX>::type ka)
+{
+    const MalaArgs<D>& m = mala_of<D>(ka);
     const StepArgs<D>& a = m.s;
     __shared__ GradShared gsh;
+    [[maybe_unused]] const MixArgs<D>* mx = nullptr;
+    [[maybe_unused]] float* stage = nullptr;
+    if constexpr (MX) {
+        __shared__ float mix_lds[MALA_MIX_STAGE<N>];
+        mx = mala_mix_of<D>(ka);
+        stage = mix_lds + (threadIdx.x & 63u);
+    }
+    // MX at theta_dim 4: reread_constants every iteration, without which the variant does not fit 256 registers
+    // (profiles/mixture_glmala_kernel_resources.txt)
+    constexpr bool REREAD = MX && D >= 4;
     const int64_t tid = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool valid = tid < a.n_chains;
     const int64_t i = valid ? tid : a.n_chains - 1;          // tail lanes shadow the last chain (no stores): the cooperative
@@ -630,11 +753,18 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) gl
 #pragma unroll
         for (int j = 0; j < D; ++j) prev[j] = (float)c.theta[j];
 
+        [[maybe_unused]] MalaArgs<D> ml;
+        if constexpr (REREAD) {
+            ml = m;
+            reread_constants<D>(ml);
+        }
+        const MalaArgs<D>& mu = REREAD ? ml : m;             // this iteration's view of the arguments
+
         glabc_u32x4 h = glabc_philox4x32_10(rng.c0, rng.c1, step, 0u, rng.k0, rng.k1);
         const float u_branch = glabc_uniform_f32(h.v[0]);
         const bool is_global = u_branch < a.gf;                                              // GLMALA.py:151
         bool moved = false;
-        if (is_global) moved = mala_isir_move<D, N>(m, rng, step, glabc_uniform_f64(h.v[2], h.v[3]), c);
+        if (is_global) moved = mala_isir_move<D, N, MX>(mu, rng, step, glabc_uniform_f64(h.v[2], h.v[3]), c, mx, stage);
         {
             float e[D], s[D], zn[2 * D];
             candidate_draws<D>(rng, step, 0, false, e, s);
@@ -643,7 +773,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) gl
                 zn[j] = e[j];
                 zn[D + j] = s[j];
             }
-            const bool mv = mala_move<D, LEAN>(m, rng, step, !is_global && valid, glabc_uniform_f32(h.v[1]), zn, c, &gsh);
+            const bool mv = mala_move<D, LEAN>(mu, rng, step, !is_global && valid, glabc_uniform_f32(h.v[1]), zn, c, &gsh);
             moved = is_global ? moved : mv;
         }
         c.n_moves += moved ? 1u : 0u;
@@ -671,25 +801,29 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) gl
     }
 
     if (!valid) return;
+    // MX: the final stores take their addresses from the chain index afresh.  The compiler otherwise keeps the 64-bit addresses of
+    // the loads above alive across the whole step loop -- in scratch, at theta_dim 4 -- to use them once more here.
+    int64_t ie = i;
+    if constexpr (MX) asm volatile("" : "+v"(ie));
 #pragma unroll
     for (int j = 0; j < D; ++j) {
-        m.theta64[j * a.stride + i] = c.theta[j];
-        m.y64[j * a.stride + i] = c.y[j];
-        m.grad[j * a.stride + i] = c.grad[j];
-        a.theta[j * a.stride + i] = (float)c.theta[j];
-        a.y[j * a.stride + i] = (float)c.y[j];
+        m.theta64[j * a.stride + ie] = c.theta[j];
+        m.y64[j * a.stride + ie] = c.y[j];
+        m.grad[j * a.stride + ie] = c.grad[j];
+        a.theta[j * a.stride + ie] = (float)c.theta[j];
+        a.y[j * a.stride + ie] = (float)c.y[j];
     }
-    m.log_w64[i] = c.log_w;
-    if (a.log_w) a.log_w[i] = (float)c.log_w;
-    a.flags[i] = c.flags;
-    if (a.n_moves) a.n_moves[i] = c.n_moves;
+    m.log_w64[ie] = c.log_w;
+    if (a.log_w) a.log_w[ie] = (float)c.log_w;
+    a.flags[ie] = c.flags;
+    if (a.n_moves) a.n_moves[ie] = c.n_moves;
     if (mom) {
 #pragma unroll
-        for (int j = 0; j < D; ++j) a.sum_theta[j * a.stride + i] = s1[j];
+        for (int j = 0; j < D; ++j) a.sum_theta[j * a.stride + ie] = s1[j];
 #pragma unroll
         for (int k = 0; k < TRI; ++k) {
-            a.sum_outer[k * a.stride + i] = s2[k];
-            a.sum_jump[k * a.stride + i] = sj[k];
+            a.sum_outer[k * a.stride + ie] = s2[k];
+            a.sum_jump[k * a.stride + ie] = sj[k];
         }
     }
 }
@@ -900,13 +1034,25 @@ GLABC_DEV void team_publish(bool need, unsigned long long mask, const float (&th
     }
 }
 
-template <int N, bool LEAN, int NW>
-__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) glmala_team_kernel(const MalaArgs<2> m)
+// MX: the mixture variant.  Its staged candidates are LDS of their own that only the main wavefront touches, between the round-1
+// publish barrier and the post-items barrier, each lane its own column: the move adds no barrier (the helpers count them) and
+// shares nothing with TeamShared, which the helpers add into meanwhile.
+template <int N, bool LEAN, int NW, bool MX = false>
+__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)))
+glmala_team_kernel(const typename MalaKernelArgs<2, MX>::type ka)
 {
     constexpr int D = 2;
+    const MalaArgs<D>& m = mala_of<D>(ka);
     const StepArgs<D>& a = m.s;
     __shared__ TeamShared sh;
     const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+    [[maybe_unused]] const MixArgs<D>* mx = nullptr;
+    [[maybe_unused]] float* stage = nullptr;
+    if constexpr (MX) {
+        __shared__ float mix_lds[MALA_MIX_STAGE<N>];
+        mx = mala_mix_of<D>(ka);
+        stage = mix_lds + lane;
+    }
     {                                                                   // accumulators start at zero (team_finish keeps them so)
         unsigned long long* z = &sh.acc[0][0][0][0];
         for (int q = (int)threadIdx.x; q < 64 * 16; q += 64 * NW) z[q] = 0ull;
@@ -1011,7 +1157,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)
         team_publish(is_local, mask1, thf, rng, 1, &sh);
         __syncthreads();
         bool moved = false;
-        if (is_global) moved = mala_isir_move<D, N>(m, rng, step, glabc_uniform_f64(hd.v[2], hd.v[3]), c);
+        if (is_global) moved = mala_isir_move<D, N, MX>(m, rng, step, glabc_uniform_f64(hd.v[2], hd.v[3]), c, mx, stage);
         team_items<LEAN, NW>(m, rng.k0, rng.k1, step, 1, __popcll(mask1), 0, lane, m.credit, &sh);
         __syncthreads();
         double gprop[D] = {0.0, 0.0};
@@ -1116,5 +1262,8 @@ template <int D>
 int launch_glmala_dim(int n_batch, const MalaArgs<D>& m, hipStream_t stream);
 template <int D>
 int launch_glmala_init_dim(const MalaArgs<D>& m, hipStream_t stream);
+// the mixture variant; defined in glabc_mala_mix_dim.hip (one TU per D)
+template <int D>
+int launch_glmala_mix_dim(int n_batch, const MalaMixArgs<D>& m, hipStream_t stream);
 
 }  // namespace glabc

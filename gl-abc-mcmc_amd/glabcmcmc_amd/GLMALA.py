@@ -2,7 +2,8 @@
 
 Same positional signature as the reference function.  The loop body (GLMALA.py:150-200) --
 including the common-random-number finite-difference gradient of GLMALA.py:46-95 -- runs in
-the fused gfx950 kernel behind ``glabc_glmala_steps`` (include/glabc.h).  Shapes, return value
+the fused gfx950 kernel behind ``glabc_glmala_steps`` (include/glabc.h), or ``glabc_glmala_mix_steps`` when the importance
+proposal is a ``GaussianMixture``.  Shapes, return value
 and keyword-only extras as in ``GLMCMC``.
 
 Reference behaviours that are reproduced on purpose: the chain's state
@@ -15,6 +16,14 @@ is a Philox sub-stream of the run's seed.
 from . import _capi, _host, engine, generic
 
 
+def fused_dispatch(ABCset, Importance_Proposal, batch_size):
+    """Does path="auto" run this call in the fused kernel?  The |theta| + noise Model up to theta_dim 4, batch sizes up to
+    GLABC_MAX_BATCH, a DiagGaussian or Uniform importance proposal (glabc_glmala_steps) or a GaussianMixture of the Model's
+    dimension with a prior that is not Gamma (glabc_glmala_mix_steps); everything else is generic.run_glmala's."""
+    return bool(generic.fused_supported(ABCset, (Importance_Proposal,), batch_size, max_dim=4, mixture_ok=True, mixture_single=True) and
+                engine.model_descriptor(ABCset).sim_kind == _capi.SIM_ABS_GAUSS)
+
+
 def GLMALA(ABCset, num_ite, Initial_theta, Initial_y, tau, num_grad,
            filelocation, global_frequency=0, Importance_Proposal=None, batch_size=None, *,
            seed=None, device=None, chain0=0, record_history=True, stats=None, return_device=False,
@@ -23,8 +32,7 @@ def GLMALA(ABCset, num_ite, Initial_theta, Initial_y, tau, num_grad,
         raise ValueError("GLMALA needs Importance_Proposal and batch_size (GLMALA.py:155,158)")
     if path not in ("auto", "fused", "generic"):
         raise ValueError("path must be 'auto', 'fused' or 'generic'")
-    fused_ok = generic.fused_supported(ABCset, (Importance_Proposal,), batch_size, max_dim=4) and \
-        engine.model_descriptor(ABCset).sim_kind == _capi.SIM_ABS_GAUSS
+    fused_ok = fused_dispatch(ABCset, Importance_Proposal, batch_size)
     if path == "generic" or (path == "auto" and not fused_ok):
         # a Model given as callbacks (generic.py): iSIR through glabc_propose / glabc_select, the MALA move's gradient
         # through the Model's generate_samples / discrepancy in float64 torch operations

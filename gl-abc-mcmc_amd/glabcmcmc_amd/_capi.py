@@ -311,6 +311,7 @@ ENTRY_POINTS = {
     "glabc_glmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_globalmcmc_mix_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_glmcmc_mix_wide_steps": (C.c_int, [_P(Model), _P(Dist), _P(Mixture), _P(Chains), _P(Run), C.c_void_p]),
+    "glabc_glmala_mix_steps": (C.c_int, [_P(Model), _P(Mixture), _P(Mala), _P(Chains), _P(Run), C.c_void_p]),
     "glabc_rtc_compile_mix": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p,
                                         C.c_int64]),
     "glabc_rtc_compile_wide_mix": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),

@@ -211,10 +211,12 @@ def glmala_init(model_desc, chains):
 
 def run_glmala_steps(model_desc, importance_desc, mala, chains, n_steps, step0, seed, global_frequency, batch_size,
                      history=None, moments=None, steps_per_launch=None, lanes_per_chain=0, mirror=None):
-    """GLMALA twin of run_steps (entry point glabc_glmala_steps); `mala` is a _capi.Mala.
+    """GLMALA twin of run_steps (entry point glabc_glmala_steps, or glabc_glmala_mix_steps when importance_desc is a
+    _capi.Mixture); `mala` is a _capi.Mala.
     lanes_per_chain: 0 = let the library choose; 1 = 64 chains per wavefront, 2 = 32 (the other 32 lanes only help with the
     wave-cooperative gradient) -- launch geometry, results are identical."""
-    lib = _capi.lib()
+    entry = "glabc_glmala_mix_steps" if isinstance(importance_desc, _capi.Mixture) else "glabc_glmala_steps"
+    fn = getattr(_capi.lib(), entry)
     k_max = int(steps_per_launch or MAX_STEPS_PER_LAUNCH)
     if mirror is not None:
         k_max = min(k_max, int(mirror.steps_per_launch(steps_per_launch)))
@@ -237,8 +239,8 @@ def run_glmala_steps(model_desc, importance_desc, mala, chains, n_steps, step0, 
                 run.hist_stride = chains.n
             if ms is not None:
                 run.moments = C.pointer(ms)
-            _capi.check(lib.glabc_glmala_steps(C.byref(model_desc), C.byref(importance_desc), C.byref(mala), C.byref(cs),
-                                               C.byref(run), C.c_void_p(stream)), "glabc_glmala_steps")
+            _capi.check(fn(C.byref(model_desc), C.byref(importance_desc), C.byref(mala), C.byref(cs), C.byref(run),
+                           C.c_void_p(stream)), entry)
             done += k
             if mirror is not None:
                 mirror.rows_done(step0 + done)

@@ -76,7 +76,8 @@ def rtc_program(ABCset, model_desc, proposal, algo, batch_size=1):
     return ABCset.program(algo, batch_size)
 
 
-def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, gamma_ok=False, mixture_ok=False, mixture_max_batch=None):
+def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, gamma_ok=False, mixture_ok=False, mixture_max_batch=None,
+                    mixture_single=False):
     """Can the fused kernels (glabc_glmcmc_steps / glabc_globalmcmc_steps / glabc_glmala_steps) run this configuration?
     gamma_ok: the entry point knows GLABC_DIST_GAMMA as the LAST proposal (importance / global) and as the Model's prior --
     GLMCMC and GlobalMCMC on the |theta| + noise Model up to theta_dim 4, on g-and-k and on a compiled.CompiledModel, whose
@@ -87,7 +88,9 @@ def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, ga
     to GLABC_MAX_BATCH proposals only, as for Gaussian proposals), batch sizes up to GLABC_MAX_BATCH, no Gamma prior; anywhere else a
     mixture stays a callback.
     mixture_max_batch: the largest batch size the caller's mixture entry points take, where that is more than GLABC_MAX_BATCH (GLMCMC:
-    glabc_glmcmc_mix_wide_steps, GLABC_MAX_BATCH_WIDE); the rest of the mixture's matrix is the same."""
+    glabc_glmcmc_mix_wide_steps, GLABC_MAX_BATCH_WIDE); the rest of the mixture's matrix is the same.
+    mixture_single: the mixture may be the ONLY proposal -- GLMALA, whose local move has no increment distribution
+    (glabc_glmala_mix_steps; the caller still asks for the |theta| + noise Model itself)."""
     m = try_descriptor(ABCset)
     if m is None or not isinstance(m, _capi.Model):
         return False
@@ -98,7 +101,7 @@ def fused_supported(ABCset, proposals, batch_size, max_batch=None, max_dim=8, ga
             # a compiled.CompiledModel: its mixture programs, any theta_dim; a user prior above GLABC_MAX_BATCH stays split-phase as below
             user = (m.sim_kind == _capi.SIM_USER and hasattr(ABCset, "program") and
                     (batch_size is None or int(batch_size) <= _capi.MAX_BATCH or not getattr(ABCset, "user_prior", False)))
-            return bool(mixture_ok and i == len(proposals) - 1 and i > 0 and d.dim == m.theta_dim and not gamma and
+            return bool(mixture_ok and i == len(proposals) - 1 and (i > 0 or mixture_single) and d.dim == m.theta_dim and not gamma and
                         ((m.sim_kind == _capi.SIM_ABS_GAUSS and m.theta_dim <= 4) or m.sim_kind == _capi.SIM_GK or user) and
                         (batch_size is None or 1 <= int(batch_size) <= (mixture_max_batch or _capi.MAX_BATCH)))
         if d is None or not isinstance(d, _capi.Dist) or d.dim != m.theta_dim:

@@ -627,6 +627,34 @@ int glabc_globalmcmc_mix_steps(const glabc_model* model, const glabc_dist* local
 int glabc_glmcmc_mix_wide_steps(const glabc_model* model, const glabc_dist* local, const glabc_mixture* importance,
                                 const glabc_chains* chains, const glabc_run* run, void* stream);
 
+/* glabc_glmala_steps with a mixture as the importance proposal of the iSIR global move (GLMALA.py:151-180); glabc_glmala_init serves
+ * it unchanged (it does not look at the proposal).  The move's proposal is the mixture exactly as glabc_glmcmc_mix_steps has it:
+ * candidate j of (chain, iteration) takes its mode uniform from the Philox block at slot GLABC_SLOT_MIX + j, eps are the candidate's
+ * ordinary proposal NORMALS (the words glabc_glmala_steps reads for a DiagGaussian proposal), z = eps * scale + loc in double,
+ * theta' = (float) z, log q' = (float) log_prob(z).  The current state's slot follows GLMALA's dtype bookkeeping (GLABC_FLAG_TH64 /
+ * GLABC_FLAG_LW64, GLMALA.py:152-156): a float32 state uses q = (float) log_prob((double) theta) and float32 weights; a float64 state
+ * uses log_prob(theta64) UNROUNDED in log_w and sets GLABC_FLAG_LW64.  The reference's GaussianMixture holds float64 parameters and
+ * would promote more than this (a float32 state's weight, every candidate's weight): as for the GLMCMC mixture entry points the
+ * density is float64, rounded once to the float32 state.  No existing draw, slot or struct changes: the MALA local move, the
+ * gradient noise slots and log_w's lifetime are glabc_glmala_steps', and a chain on the local branch computes exactly what it
+ * computes there.
+ * Scope: GLABC_SIM_ABS_GAUSS with theta_dim 1..4, batch size 1..GLABC_MAX_BATCH, 1..GLABC_MAX_MODES modes, a DiagGaussian or Uniform
+ * prior, lanes_per_chain 0 / 1 / 2 as for glabc_glmala_steps, with history and moments.
+ * Checks, first defect wins (glabc_glmala_steps' order, the mixture's own checks where it checks its importance proposal):
+ *   the model (a null pointer GLABC_ERR_NULL, then what glabc_glmala_steps refuses of a model: a Gamma prior is GLABC_ERR_KIND);
+ *   sim_kind != GLABC_SIM_ABS_GAUSS (GLABC_ERR_KIND); theta_dim 5..8 (GLABC_ERR_DIM, the status glabc_glmala_steps gives it, but
+ *   here ahead of everything that follows);
+ *   the mixture: null (GLABC_ERR_NULL), n_modes outside 1..GLABC_MAX_MODES (GLABC_ERR_ARG), dim != theta_dim (GLABC_ERR_DIM), its
+ *   tables as glabc_glmcmc_mix_steps checks them (GLABC_ERR_ARG);
+ *   null mala / run (GLABC_ERR_NULL); the chains' pointers, theta64 / y64 / log_w64 / grad / flags included (GLABC_ERR_NULL), and range
+ *   (GLABC_ERR_ARG); n_steps < 0 or a batch size outside 1..GLABC_MAX_BATCH (GLABC_ERR_ARG); a NaN global_frequency (GLABC_ERR_ARG);
+ *   global_frequency_per_chain (GLABC_ERR_ARG); num_grad outside 2..65536, tau not finite and > 0, tau_sq not finite, eps_sq not
+ *   finite and >= 0 (GLABC_ERR_ARG); hist_stride < n_chains (GLABC_ERR_ARG); incomplete moments (GLABC_ERR_NULL); a tape,
+ *   GLABC_MATH_FAST or dump_draws (GLABC_ERR_ARG); lanes_per_chain outside 0..2 (GLABC_ERR_ARG); step0 + n_steps past 2^32
+ *   (GLABC_ERR_ARG).  Then n_chains == 0 or n_steps == 0 returns GLABC_OK and touches nothing. */
+int glabc_glmala_mix_steps(const glabc_model* model, const glabc_mixture* importance, const glabc_mala* mala,
+                           const glabc_chains* chains, const glabc_run* run, void* stream);
+
 /* The mixture variant around a USER simulator (GLABC_SIM_USER): glabc_rtc_compile / glabc_rtc_compile_wide with the kernels of the
  * three entry points above instead of the generic ones -- sampler_kernel<.., VAR_MIX> at one lane per chain for one (algorithm,
  * batch size 1..GLABC_MAX_BATCH), or the lane-group kernel's mixture variant at 8 / 16 / 32 / 64 lanes per chain for any batch size

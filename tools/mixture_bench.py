@@ -10,8 +10,12 @@ one of seconds per iteration, and each entry names its own iteration count.
 --compiled runs the same calls on a CompiledModel whose source is the |theta| + noise simulator: (a) is then the run-time compiled
 mixture program (glabc_rtc_mix_steps), (b) the callback path such a call took before those programs existed.
 
+--glmala runs whole GLMALA calls instead (bench.py's glmala workload: gf 0.8, tau 0.3, num_grad 100): (a) is glabc_glmala_mix_steps,
+(b) generic.run_glmala with the mixture as a callback and the MALA gradient as float64 torch operations -- what path="auto" ran before
+the kernel variant existed --, (c) glabc_glmala_steps with a DiagGaussian importance proposal: the price of the K-mode density.
+
     python tools/mixture_bench.py [--chains 65536] [--iters 2000] [--split-iters ITERS] [--batch 5] [--repeats 3] [--compiled]
-                                  [--out profiles/mixture_bench.json]
+                                  [--glmala] [--out profiles/mixture_bench.json]
 """
 import argparse
 import json
@@ -54,6 +58,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup-iters", type=int, default=20)
     ap.add_argument("--compiled", action="store_true", help="a CompiledModel with the |theta| + noise simulator as C source")
+    ap.add_argument("--glmala", action="store_true", help="whole GLMALA calls (gf 0.8, tau 0.3, num_grad 100) instead of GLMCMC")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -68,7 +73,12 @@ def main():
     y0 = th0.abs() + (0.05 ** 0.5) * torch.randn(a.chains, 2, generator=gen)
     kw = dict(seed=20261019, verbose=False, record_history=False)
 
+    if a.glmala and a.compiled:
+        ap.error("--glmala runs on Mixture_set: GLMALA has no run-time compiled kernels")
+
     def call(ip, path, iters):
+        if a.glmala:
+            return lambda: g.GLMALA(model, iters + 1, th0, y0, 0.3, 100, None, 0.8, ip, a.batch, path=path, **kw)
         return lambda: g.GLMCMC(model, iters + 1, th0, y0, lp, None, 0.9, ip, a.batch, path=path, **kw)
 
     iters = {"fused_mixture": a.iters, "split_phase_mixture": a.split_iters or a.iters, "fused_diag_gaussian": a.iters}
@@ -81,8 +91,9 @@ def main():
     for _ in range(a.repeats):                               # (a) and (b) alternate; (c) rides along
         for name in ("fused_mixture", "split_phase_mixture", "fused_diag_gaussian"):
             times[name].append(clocked(runs[name]))
-    res = {"workload": "GLMCMC on %s, theta_dim 2, 4-mode GaussianMixture importance proposal"
-                       % ("a CompiledModel (|theta| + noise as C source)" if a.compiled else "Mixture_set"), "chains": a.chains,
+    res = {"workload": "%s on %s, theta_dim 2, 4-mode GaussianMixture importance proposal"
+                       % ("GLMALA (gf 0.8, tau 0.3, num_grad 100)" if a.glmala else "GLMCMC",
+                          "a CompiledModel (|theta| + noise as C source)" if a.compiled else "Mixture_set"), "chains": a.chains,
            "iterations": a.iters, "batch_size": a.batch, "repeats": a.repeats, "device": torch.cuda.get_device_name(0)}
     for name, ts in times.items():
         k = float(iters[name])
