@@ -232,6 +232,17 @@ inline int check_propose_mix(int algo, const glabc_dist* local, const glabc_mixt
     return GLABC_OK;
 }
 
+// ---- glabc_autocov: a chain-major history and its two dense outputs, in the order include/glabc.h lists the refusals ----------------
+inline int check_autocov(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t max_lag,
+                         const double* mean_out, const double* acov_out)
+{
+    if (!history || !mean_out || !acov_out) return GLABC_ERR_NULL;
+    if (theta_dim < 1 || theta_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    if (n_rows < 1 || n_chains < 0 || stride < n_chains) return GLABC_ERR_ARG;
+    if (max_lag < 0 || max_lag > n_rows - 1 || max_lag > GLABC_MAX_LAG) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------
 inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
                          const glabc_run* r)

@@ -707,6 +707,32 @@ int glabc_esjd(const float* history, int64_t n_rows, int32_t theta_dim, int64_t 
 int glabc_moments_esjd(const glabc_moments* moments, int64_t n_steps, int32_t theta_dim, int64_t n_chains,
                        int64_t stride, float* esjd_out, void* stream);
 
+/* ---- chain diagnostics: per-chain means and lagged autocovariances of a history, the sufficient statistics of split-R-hat and
+ * of the effective sample size (glabcmcmc_amd/diagnostics.py forms both from them).
+ *
+ * history is [n_rows][theta_dim][stride] float32, chain-major: what the samplers write and glabc_esjd reads; columns
+ * n_chains .. stride - 1 are never read.  The outputs are dense, with output stride n_chains:
+ *     mean_out[j * n_chains + c]                          j < theta_dim
+ *     acov_out[(k * theta_dim + j) * n_chains + c]        k = 0 .. max_lag
+ *
+ * Numerical specification.  For every chain c and coordinate j, with x_t = history[t][j][c]: all arithmetic is IEEE double, every
+ * line is one rounded operation in the stated order, and there is no FMA (the object is built with -ffp-contract=off, as the
+ * rest of the numerical contract is):
+ *     S = 0.0;    for t = 0 .. n_rows - 1 ascending:  S = S + (double) x_t;            m = S / (double) n_rows
+ *     u_t = (double) x_t - m
+ *     A_k = 0.0;  for t = k .. n_rows - 1 ascending:  A_k = A_k + u_t * u_{t-k};        acov_k = A_k / (double) n_rows
+ * (the biased 1/n normalisation of Geyer and of Stan).  The order is fixed per (chain, coordinate, lag), so the result does not
+ * depend on the launch geometry, and a float64 loop on the host reproduces it bit for bit.  A NaN or an infinity in a chain makes
+ * that chain's mean of that coordinate non-finite and acov_k NaN at every lag that pairs the row with another (all of them when
+ * the row is the first or max_lag is at most its index), as the lines above say; no other chain or coordinate is touched.
+ *
+ * Refusals, in this order; a refused call launches nothing and writes nothing: a null pointer GLABC_ERR_NULL; theta_dim outside
+ * 1 .. GLABC_MAX_DIM GLABC_ERR_DIM; n_rows < 1, n_chains < 0, stride < n_chains, max_lag < 0, max_lag > n_rows - 1 or
+ * max_lag > GLABC_MAX_LAG GLABC_ERR_ARG.  n_chains == 0 returns GLABC_OK and writes nothing. */
+#define GLABC_MAX_LAG 4096
+int glabc_autocov(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride,
+                  int32_t max_lag, double* mean_out, double* acov_out, void* stream);
+
 /* ---- KernelDensity, the adaptive proposal of AGLMCMC (kernel_density.py:4-177) --------
  * A weighted Gaussian KDE over n_samples centres.  All arrays are device pointers; x is dimension-major.
  *
