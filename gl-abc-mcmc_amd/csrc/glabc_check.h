@@ -243,6 +243,49 @@ inline int check_autocov(const float* history, int64_t n_rows, int32_t theta_dim
     return GLABC_OK;
 }
 
+// ---- glabc_key_counts / glabc_histogram: the history of glabc_autocov and a table of counts, in the order include/glabc.h lists
+// the refusals.  The levels of the radix selection: (prefix bits, digit bits) = (0, 11), (11, 11), (22, 10)
+constexpr int key_prefix_bits(int level) { return 11 * level; }
+constexpr int key_digit_bits(int level) { return level == 2 ? 10 : 11; }
+constexpr uint32_t KEY_UNUSED_SLOT = 0xFFFFFFFFu;
+
+inline int check_counts_history(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride,
+                                const void* host_table, const void* host_table2, const uint64_t* counts)
+{
+    if (!history || !host_table || !host_table2 || !counts) return GLABC_ERR_NULL;
+    if (theta_dim < 1 || theta_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    if (n_rows < 1 || n_chains < 0 || stride < n_chains) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
+inline int check_key_counts(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t level,
+                            int32_t n_prefixes, const uint32_t* prefixes, const uint64_t* counts)
+{
+    if (int e = check_counts_history(history, n_rows, theta_dim, n_chains, stride, prefixes, prefixes, counts)) return e;
+    if (level < 0 || level > 2) return GLABC_ERR_ARG;
+    if (n_prefixes < 1 || n_prefixes > GLABC_MAX_PREFIXES || (level == 0 && n_prefixes != 1)) return GLABC_ERR_ARG;
+    if (level == 0) return GLABC_OK;                              // the prefix word is ignored
+    for (int j = 0; j < theta_dim; ++j)
+        for (int s = 0; s < n_prefixes; ++s) {
+            const uint32_t p = prefixes[j * n_prefixes + s];
+            if (p == KEY_UNUSED_SLOT) continue;
+            if ((p >> key_prefix_bits(level)) != 0) return GLABC_ERR_ARG;
+            for (int q = 0; q < s; ++q)
+                if (prefixes[j * n_prefixes + q] == p) return GLABC_ERR_ARG;
+        }
+    return GLABC_OK;
+}
+
+inline int check_histogram(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_bins,
+                           const double* lo, const double* hi, const uint64_t* counts)
+{
+    if (int e = check_counts_history(history, n_rows, theta_dim, n_chains, stride, lo, hi, counts)) return e;
+    if (n_bins < 1 || n_bins > GLABC_MAX_BINS) return GLABC_ERR_ARG;
+    for (int j = 0; j < theta_dim; ++j)
+        if (!std::isfinite(lo[j]) || !std::isfinite(hi[j]) || !(lo[j] < hi[j])) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------
 inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
                          const glabc_run* r)

@@ -29,8 +29,18 @@ of the 2M half-chains of length n // 2 (rows [0, n // 2) and [n - n // 2, n)).
 different chains all-reduce ``pack(terms)`` (or gather it with ``parallel.gather_rows``) and every rank evaluates ``rhat`` /
 ``ess`` of the whole job.
 
-Out of scope: rank-normalised bulk / tail ESS, per-chain ESS (``autocovariance`` returns the per-chain numbers), and
-accumulating lagged products inside the sampler kernels.
+Posterior quantiles and marginal histograms.  ``quantile`` / ``interval`` / ``order_statistics`` / ``histogram`` read the same
+history in place and give what ``numpy.sort`` of all T * C draws of a coordinate would, exactly, without sorting: a radix
+selection on an order-preserving uint32 key of the float32 values (include/glabc.h: -0 and +0 are one value, NaNs sort last) in
+three passes of 11, 11 and 10 bits.  Each pass is one ``glabc_key_counts`` launch (csrc/glabc_quant.hip) that counts, per
+coordinate and per wanted key prefix, how many values fall on each digit; ``select`` walks the cumulative counts on the host.
+The counts are integers: the same bits in every launch geometry, and additive over shards of chains, so a sharded job passes
+``select`` a ``count_fn`` that all-reduces ``key_counts`` of its shard and every rank walks the same prefixes to the exact
+quantiles of the whole job.  ``histogram`` is one ``glabc_histogram`` launch, its default range the exact minimum and maximum.
+No slab of chains is ever cut for these: the kernels index with 64-bit scalars and size their own grid.
+
+Out of scope: rank-normalised bulk / tail ESS (selection gives a few ranks, not all of them), per-chain ESS (``autocovariance``
+returns the per-chain numbers), joint histograms, weighted draws, and accumulating lagged products inside the sampler kernels.
 """
 import ctypes as C
 from collections import namedtuple
@@ -47,6 +57,12 @@ _SLAB_BYTES = 256 << 20           # device scratch of one glabc_autocov call ins
 # additive over shards of chains (M adds up, n and half_n must agree); the half_* fields have a leading axis of 2
 Terms = namedtuple("Terms", "M n sum_mean sum_mean_sq sum_acov half_n half_sum_mean half_sum_mean_sq half_sum_acov0")
 Ess = namedtuple("Ess", "ess tau truncated max_lag")
+
+KEY_LEVELS = ((0, 11), (11, 11), (22, 10))         # (prefix bits, digit bits) of the three passes, include/glabc.h
+MAX_PREFIXES = 8                  # GLABC_MAX_PREFIXES: prefixes per coordinate of one glabc_key_counts launch
+MAX_BINS = 4096                   # GLABC_MAX_BINS
+UNUSED_PREFIX = 0xFFFFFFFF        # a slot of a prefix table that counts nothing; also the key of every NaN
+Histogram = namedtuple("Histogram", "counts edges below above nan")
 
 
 # ---------------------------------------------------------------------------------- arguments
@@ -269,3 +285,206 @@ def summary(history, max_lag=None, layout="rows"):
         sd = np.sqrt(var)
         return {"mean": t.sum_mean / t.M, "sd": sd, "mcse": sd / np.sqrt(e.ess), "rhat": rhat(t, split=True), "ess": e.ess,
                 "tau": e.tau, "truncated": e.truncated}
+
+
+# ---------------------------------------------------------------------------------- quantiles: the device part
+def _check_prefixes(level, prefixes, d):
+    """-> uint32 [D][P] (level 0: one ignored word per coordinate)"""
+    if level != int(level) or not 0 <= level <= 2:
+        raise ValueError("level is 0, 1 or 2, got %r" % (level,))
+    if level == 0:
+        if prefixes is not None and np.shape(prefixes) != (d, 1):
+            raise ValueError("level 0 has no prefixes (None, or one ignored word per coordinate), got shape %r" % (np.shape(prefixes),))
+        return np.zeros((d, 1), np.uint32)
+    table = np.asarray(prefixes)
+    if table.ndim != 2 or table.shape[0] != d or table.shape[1] < 1 or table.dtype.kind not in "ui":
+        raise ValueError("prefixes are integers [D = %d][P >= 1], got shape %r of %s" % (d, table.shape, table.dtype))
+    table = table.astype(np.int64)
+    used = table != UNUSED_PREFIX
+    if ((table < 0) | (used & (table >> KEY_LEVELS[level][0] != 0))).any():
+        raise ValueError("a level-%d prefix has %d bits (or is 0xFFFFFFFF, unused)" % (level, KEY_LEVELS[level][0]))
+    for row in table:
+        if len(np.unique(row[row != UNUSED_PREFIX])) != (row != UNUSED_PREFIX).sum():
+            raise ValueError("the used prefixes of a coordinate must be distinct")
+    return table.astype(np.uint32)
+
+
+def _key_counts(h, level, table):
+    """glabc_key_counts on the chain-major rows `h`, at most MAX_PREFIXES columns of `table` per launch -> uint64 [D][P][2^digit_bits]"""
+    n_rows, d, stride = h.shape
+    bins = 1 << KEY_LEVELS[level][1]
+    out = np.zeros((d, table.shape[1], bins), np.uint64)
+    stream = torch.cuda.current_stream(h.device).cuda_stream
+    with torch.cuda.device(h.device):
+        for p0 in range(0, table.shape[1], MAX_PREFIXES):
+            part = np.ascontiguousarray(table[:, p0:p0 + MAX_PREFIXES])
+            k = part.shape[1]
+            counts = torch.zeros(d, k, bins, dtype=torch.int64, device=h.device)
+            _capi.check(_capi.lib().glabc_key_counts(h.data_ptr(), n_rows, d, stride, stride, int(level), k, part.ctypes.data,
+                                                     counts.data_ptr(), C.c_void_p(stream)), "glabc_key_counts")
+            out[:, p0:p0 + k] = counts.cpu().numpy().view(np.uint64)
+    return out
+
+
+def key_counts(history, level, prefixes=None, layout="rows"):
+    """-> uint64 [D][P][2^digit_bits]: per coordinate and prefix, how many of the history's values (all rows, all chains) belong to
+    the prefix and have each digit of `level` (include/glabc.h; level 0: P = 1, every value).  A prefix of 0xFFFFFFFF is an unused
+    slot, its row stays zero.  Additive over shards of chains: what a sharded job all-reduces inside the count_fn of `select`"""
+    _, _, d, _ = _check(history, layout, 0)
+    table = _check_prefixes(level, prefixes, d)
+    return _key_counts(_chain_major(history, layout), int(level), table)
+
+
+# ---------------------------------------------------------------------------------- quantiles: the host driver
+def unkey(keys):
+    """float32 values of uint32 keys: +0.0 for the zero's key, NaN for 0xFFFFFFFF"""
+    k = np.asarray(keys, np.uint32)
+    u = np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32)
+    return np.where(k == np.uint32(UNUSED_PREFIX), np.float32(np.nan), u.view(np.float32))
+
+
+def _walk(count_fn, ranks_of):
+    """The radix selection.  ranks_of(N [D], n_nan [D]) -> int64 ranks [R][D], asked once the level-0 counts are there;
+    -> (float32 order statistics [R][D], N [D], n_nan [D])"""
+    prefix = rem = slot = None
+    for level, (prefix_bits, digit_bits) in enumerate(KEY_LEVELS):
+        if level == 0:
+            counts = np.asarray(count_fn(0, None)).astype(np.int64)
+            if counts.ndim != 3 or counts.shape[1:] != (1, 1 << digit_bits):
+                raise ValueError("count_fn(0, None) must return [D][1][%d] counts, got shape %r" % (1 << digit_bits, counts.shape))
+            d = counts.shape[0]
+            total, n_nan = counts[:, 0].sum(axis=1), counts[:, 0, -1].copy()          # the last level-0 digit holds the NaNs alone
+            rem = np.array(ranks_of(total, n_nan), np.int64).reshape(-1, d)
+            if ((rem < 0) | (rem >= total)).any():
+                raise ValueError("a rank outside 0..N - 1 = %d" % (int(total.min()) - 1))
+            prefix, slot = np.zeros(rem.shape, np.int64), np.zeros(rem.shape, np.int64)
+        else:
+            distinct = [np.unique(prefix[:, j]) for j in range(d)]                    # deduplicated per coordinate, ascending
+            table = np.full((d, max(1, max(len(u) for u in distinct))), UNUSED_PREFIX, np.uint32)
+            for j, u in enumerate(distinct):
+                table[j, :len(u)] = u
+                slot[:, j] = np.searchsorted(u, prefix[:, j])
+            counts = np.asarray(count_fn(level, table)).astype(np.int64)
+            if counts.shape != (d, table.shape[1], 1 << digit_bits):
+                raise ValueError("count_fn(%d, prefixes) must return %r counts, got shape %r"
+                                 % (level, (d, table.shape[1], 1 << digit_bits), counts.shape))
+        cum = np.cumsum(counts, axis=2)
+        for r in range(rem.shape[0]):
+            for j in range(d):
+                row = cum[j, slot[r, j]]
+                digit = int(np.searchsorted(row, rem[r, j], side="right"))             # the first digit with cum > remaining rank
+                if digit >= row.size:
+                    raise RuntimeError("the level-%d counts of prefix %#x hold %d values, rank %d is not among them: count_fn is "
+                                       "inconsistent between levels" % (level, prefix[r, j], row[-1], rem[r, j]))
+                rem[r, j] -= row[digit - 1] if digit else 0
+                prefix[r, j] = (prefix[r, j] << digit_bits) | digit
+    return unkey(prefix.astype(np.uint32)), total, n_nan
+
+
+def _check_q(q):
+    q = np.atleast_1d(np.asarray(q, np.float64))
+    if q.ndim != 1 or not ((q >= 0.0) & (q <= 1.0)).all():
+        raise ValueError("quantiles are numbers in [0, 1], got %r" % (q,))
+    return q
+
+
+def _check_ranks(ranks, n=None):
+    r = np.atleast_1d(np.asarray(ranks))
+    if r.ndim != 1 or r.dtype.kind not in "ui" or (r.astype(np.int64) < 0).any() or (n is not None and (r.astype(np.int64) >= n).any()):
+        raise ValueError("ranks are integers in 0..N - 1%s, got %r" % ("" if n is None else " = %d" % (n - 1), ranks))
+    return r.astype(np.int64)
+
+
+def select(count_fn, ranks=None, q=None):
+    """Exact order statistics from digit counts.  count_fn(level, prefixes) -> counts [D][P][2^digit_bits] is called once per
+    level (0, 1, 2; prefixes is None at level 0, else uint32 [D][P] with unused slots 0xFFFFFFFF) -- ``key_counts`` of a history,
+    or the all-reduced sum of the shards' ``key_counts``.  At each level the digit d of a rank is the first with cum[d] > the
+    remaining rank, the remaining rank drops by cum[d - 1] and the prefix becomes (prefix << digit_bits) | d.
+    ranks: integers in 0..N - 1 -> float32 [R][D], the order statistics themselves.
+    q: numbers in [0, 1] -> float64 [Q][D] by NumPy's default linear rule, h = q (N - 1), x_lo + (h - floor(h)) (x_hi - x_lo)
+    with x_lo, x_hi the order statistics of ranks floor(h) and min(floor(h) + 1, N - 1); NaN where the coordinate holds a NaN."""
+    if (ranks is None) == (q is None):
+        raise ValueError("select takes ranks or q, one of them")
+    if ranks is not None:
+        r = _check_ranks(ranks)
+        return _walk(count_fn, lambda total, n_nan: np.repeat(r[:, None], len(total), axis=1))[0]
+    q = _check_q(q)
+
+    def ranks_of(total, n_nan):
+        h = q[:, None] * (total[None, :] - 1.0)
+        lo = np.floor(h).astype(np.int64)
+        return np.concatenate([lo, np.minimum(lo + 1, total[None, :] - 1)])
+    x, total, n_nan = _walk(count_fn, ranks_of)
+    x = x.astype(np.float64)
+    h = q[:, None] * (total[None, :] - 1.0)
+    with np.errstate(invalid="ignore"):
+        out = x[:len(q)] + (h - np.floor(h)) * (x[len(q):] - x[:len(q)])
+    out[:, n_nan > 0] = np.nan
+    return out
+
+
+def _counter(history, layout):
+    """count_fn of a history, staged once"""
+    h = _chain_major(history, layout)
+    return lambda level, table: _key_counts(h, level, np.zeros((h.shape[1], 1), np.uint32) if table is None else table)
+
+
+def order_statistics(history, ranks, layout="rows"):
+    """-> float32 [R][D]: element ranks[r] of each coordinate's T * C draws in ascending order (NaNs last), exactly"""
+    n, c, _, _ = _check(history, layout, 0)
+    r = _check_ranks(ranks, n * c)
+    return select(_counter(history, layout), ranks=r)
+
+
+def quantile(history, q, layout="rows"):
+    """-> float64 [Q][D]: numpy.quantile(draws, q) of each coordinate's T * C draws (the default linear rule, see select)"""
+    _check(history, layout, 0)
+    q = _check_q(q)
+    return select(_counter(history, layout), q=q)
+
+
+def interval(history, prob=0.95, layout="rows"):
+    """-> (lower [D], upper [D]): the equal-tailed credible interval, the quantiles at (1 - prob) / 2 and (1 + prob) / 2"""
+    _check(history, layout, 0)
+    if not 0.0 < prob < 1.0:
+        raise ValueError("prob must be in (0, 1), got %r" % (prob,))
+    lower, upper = quantile(history, ((1.0 - prob) / 2.0, (1.0 + prob) / 2.0), layout)
+    return lower, upper
+
+
+def histogram(history, bins=64, range=None, layout="rows"):
+    """-> Histogram(counts uint64 [D][bins], edges float64 [D][bins + 1], below, above, nan uint64 [D]): `bins` equal bins per
+    coordinate over `range` = (lo, hi) or [D][2], the last one closed as NumPy's; values under lo, over hi and NaNs are counted
+    apart.  range=None: each coordinate's exact minimum and maximum (NaNs aside), a constant coordinate widened by +-0.5"""
+    _, _, d, _ = _check(history, layout, 0)
+    if isinstance(bins, bool) or bins != int(bins) or not 1 <= bins <= MAX_BINS:
+        raise ValueError("bins must be an integer in 1..%d, got %r" % (MAX_BINS, bins))
+    bins = int(bins)
+    if range is not None:
+        try:
+            lim = np.array(np.broadcast_to(np.asarray(range, np.float64), (d, 2)))
+        except (TypeError, ValueError):
+            raise ValueError("range is (lo, hi) or [D = %d][2], got %r" % (d, range)) from None
+        if not (np.isfinite(lim).all() and (lim[:, 0] < lim[:, 1]).all()):
+            raise ValueError("range needs finite lo < hi, got %r" % (range,))
+    h = _chain_major(history, layout)
+    if range is None:
+        def first_and_last(total, n_nan):
+            if (total == n_nan).any():
+                raise ValueError("a coordinate holds nothing but NaN: no range to bin")
+            return np.stack([np.zeros_like(total), total - n_nan - 1])
+        ends, _, _ = _walk(_counter(h, "chain_major"), first_and_last)
+        lim = np.ascontiguousarray(ends.astype(np.float64).T)
+        if not np.isfinite(lim).all():
+            raise ValueError("the draws' range %r is not finite: pass range=" % (lim.tolist(),))
+        lim[lim[:, 0] == lim[:, 1]] += (-0.5, 0.5)
+    lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+    n_rows, _, stride = h.shape
+    counts = torch.zeros(d, bins + 3, dtype=torch.int64, device=h.device)
+    with torch.cuda.device(h.device):
+        _capi.check(_capi.lib().glabc_histogram(h.data_ptr(), n_rows, d, stride, stride, bins, lo.ctypes.data, hi.ctypes.data,
+                                                counts.data_ptr(), C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)),
+                    "glabc_histogram")
+    counts = counts.cpu().numpy().view(np.uint64)
+    edges = np.stack([np.linspace(lo[j], hi[j], bins + 1) for j in np.arange(d)])
+    return Histogram(counts[:, :bins].copy(), edges, counts[:, bins].copy(), counts[:, bins + 1].copy(), counts[:, bins + 2].copy())

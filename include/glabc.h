@@ -733,6 +733,46 @@ int glabc_moments_esjd(const glabc_moments* moments, int64_t n_steps, int32_t th
 int glabc_autocov(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride,
                   int32_t max_lag, double* mean_out, double* acov_out, void* stream);
 
+/* ---- posterior quantiles and marginal histograms of a history: integer counts, exact and additive over shards of chains and
+ * slices of rows (glabcmcmc_amd/diagnostics.py drives a three-pass radix selection with them).  The history is glabc_autocov's:
+ * [n_rows][theta_dim][stride] float32, columns n_chains .. stride - 1 never read; its base needs 4-byte alignment only.
+ *
+ * Key.  The order-preserving uint32 of a float32 x with bit pattern u: x == 0 takes the bits of +0.0 (-0 and +0 are one value);
+ * key = ~u when the sign bit is set and u | 0x80000000 otherwise; every NaN has key 0xFFFFFFFF (NaNs sort last, as in
+ * numpy.sort).  unkey is the inverse: +0.0 for the zero's key, a NaN for 0xFFFFFFFF.
+ *
+ * Levels.  Level 0, 1, 2 is (prefix bits, digit bits) = (0, 11), (11, 11), (22, 10).  A value with key k belongs to prefix p at
+ * a level when the level has no prefix bits or k >> (32 - prefix_bits) == p; its digit is
+ * (k >> (32 - prefix_bits - digit_bits)) & (2^digit_bits - 1).
+ *
+ * glabc_key_counts: for every coordinate j and slot s < n_prefixes, ADDS to counts[(j * n_prefixes + s) << digit_bits | digit]
+ * the number of values of coordinate j that belong to prefixes[j * n_prefixes + s] -- the caller zeroes `counts`, so slabs of
+ * chains and slices of rows accumulate into one table.  `prefixes` is a HOST array (it travels as kernel arguments), `counts` a
+ * device array of uint64.  A slot holding 0xFFFFFFFF is unused: its row of counts is not touched.  Level 0 needs n_prefixes == 1
+ * and ignores the prefix word.  The counts are integers, so they are the same bits whatever the launch geometry and the order
+ * of the atomic adds.
+ *
+ * Refusals, in this order; a refused call launches nothing and writes nothing: a null pointer GLABC_ERR_NULL; theta_dim outside
+ * 1 .. GLABC_MAX_DIM GLABC_ERR_DIM; n_rows < 1, n_chains < 0, stride < n_chains, level outside 0 .. 2, n_prefixes outside
+ * 1 .. GLABC_MAX_PREFIXES (or not 1 at level 0), a used prefix >= 2^prefix_bits, or two equal used prefixes of one coordinate
+ * GLABC_ERR_ARG.  n_chains == 0 returns GLABC_OK and writes nothing. */
+#define GLABC_MAX_PREFIXES 8
+int glabc_key_counts(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t level,
+                     int32_t n_prefixes, const uint32_t* prefixes, uint64_t* counts, void* stream);
+
+/* glabc_histogram: per coordinate j, n_bins equal bins over [lo[j], hi[j]] and three more slots, counts[j * (n_bins + 3) + slot]
+ * (device, uint64; the call ADDS, the caller zeroes).  lo and hi are HOST arrays.  Numerical specification, IEEE double, every
+ * operation rounded once, no FMA:
+ *     scale = (double) n_bins / (hi - lo)                                  on the host, per coordinate
+ *     u = ((double) x - lo) * scale;   b = (int64) floor(u)                per value
+ *     NaN -> slot n_bins + 2;  x < lo -> slot n_bins (below);  x > hi -> slot n_bins + 1 (above);
+ *     x == hi -> bin n_bins - 1 (NumPy's closed last bin);  otherwise bin min(b, n_bins - 1)
+ * Refusals as for glabc_key_counts, with GLABC_ERR_ARG for n_bins outside 1 .. GLABC_MAX_BINS and for a lo or hi that is not
+ * finite or not lo < hi. */
+#define GLABC_MAX_BINS 4096
+int glabc_histogram(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_bins,
+                    const double* lo, const double* hi, uint64_t* counts, void* stream);
+
 /* ---- KernelDensity, the adaptive proposal of AGLMCMC (kernel_density.py:4-177) --------
  * A weighted Gaussian KDE over n_samples centres.  All arrays are device pointers; x is dimension-major.
  *
