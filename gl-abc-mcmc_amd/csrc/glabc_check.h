@@ -286,6 +286,22 @@ inline int check_histogram(const float* history, int64_t n_rows, int32_t theta_d
     return GLABC_OK;
 }
 
+// ---- glabc_abc_draws: the Model a fused rejection draw is compiled for and the range of draws, in the order include/glabc.h lists
+// the refusals.  The parameters' values are not looked at: a draw from a prior of scale 0 or NaN is what the arithmetic says it is
+inline int check_abc_draws(const glabc_model* m, int64_t row0, const int64_t* ids, int64_t n, int64_t stride, const float* theta_out,
+                           const float* y_out, const float* dis_out, const uint8_t* accept_out)
+{
+    if (!m || (!theta_out && !y_out && !dis_out && !accept_out)) return GLABC_ERR_NULL;
+    if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    if (m->sim_kind == GLABC_SIM_GK && (m->theta_dim != 4 || m->y_dim != 8)) return GLABC_ERR_DIM;
+    if (m->sim_kind == GLABC_SIM_ABS_GAUSS && m->y_dim != m->theta_dim) return GLABC_ERR_DIM;
+    if (m->sim_kind != GLABC_SIM_ABS_GAUSS && m->sim_kind != GLABC_SIM_GK) return GLABC_ERR_KIND;
+    if (m->prior.kind != GLABC_DIST_DIAG_GAUSS && m->prior.kind != GLABC_DIST_UNIFORM) return GLABC_ERR_KIND;
+    if (m->prior.dim != m->theta_dim) return GLABC_ERR_KIND;
+    if (n < 0 || stride < n || row0 < 0 || (ids && row0 != 0)) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------
 inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
                          const glabc_run* r)

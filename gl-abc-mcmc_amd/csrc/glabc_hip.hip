@@ -20,6 +20,7 @@
 
 #include "glabc_check.h"
 #include "glabc_dispatch.h"
+#include "glabc_forward.h"
 #include "glabc_launch.h"
 #include "glabc_mala.h"
 #include "glabc_mix.h"
@@ -304,21 +305,9 @@ __global__ void __launch_bounds__(256) dist_forward_kernel(const ForwardArgs<D> 
 {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= a.n) return;
-    const uint64_t gid = (uint64_t)(a.row0 + r);
     constexpr int NB = (D + 3) / 4;
     float e[4 * NB], noise[D];
-    const bool uni = a.g.kind == GLABC_DIST_UNIFORM;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        glabc_u32x4 w = glabc_philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), 0u, (uint32_t)b, a.seed_lo, a.seed_hi);
-        float n0, n1, n2, n3;
-        glabc_normal_pair(w.v[0], w.v[1], &n0, &n1);
-        glabc_normal_pair(w.v[2], w.v[3], &n2, &n3);
-        e[4 * b] = uni ? glabc_uniform_f32(w.v[0]) : n0;
-        e[4 * b + 1] = uni ? glabc_uniform_f32(w.v[1]) : n1;
-        e[4 * b + 2] = uni ? glabc_uniform_f32(w.v[2]) : n2;
-        e[4 * b + 3] = uni ? glabc_uniform_f32(w.v[3]) : n3;
-    }
+    dist_forward_variates<D>(a.g, (uint64_t)(a.row0 + r), a.seed_lo, a.seed_hi, e);      // glabc_forward.h: glabc_abc_draws draws the same
 #pragma unroll
     for (int j = 0; j < D; ++j) {
         noise[j] = e[j];

@@ -25,6 +25,8 @@ SIM_USER = 2
 RTC_PRIOR_LOG_PROB, RTC_DISCREPANCY, RTC_LOG_KERNEL = 0, 1, 2      # glabc_rtc_model_rows `what`
 RTC_GAMMA = 1                  # glabc_rtc_compile_ex / glabc_rtc_compile_wide_ex `flags`
 VERSION = 301                  # include/glabc.h GLABC_VERSION
+ABC_NOISE_KEY = 0x9E3779B97F4A7C15      # include/glabc.h GLABC_ABC_NOISE_KEY / GLABC_ABC_ACCEPT_KEY: glabc_abc_draws
+ABC_ACCEPT_KEY = 0xD1B54A32D192ED03
 STREAM_LAYOUT = 2              # include/glabc.h GLABC_STREAM_LAYOUT
 
 FLAG_LOCAL = 1
@@ -327,6 +329,8 @@ ENTRY_POINTS = {
                                    C.c_void_p]),
     "glabc_histogram": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "glabc_abc_draws": (C.c_int, [_P(Model), C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
     "glabc_selftest_numerics": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "glabc_selftest_sqrt": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "glabc_selftest_rowsum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

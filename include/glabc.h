@@ -773,6 +773,43 @@ int glabc_key_counts(const float* history, int64_t n_rows, int32_t theta_dim, in
 int glabc_histogram(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_bins,
                     const double* lo, const double* hi, uint64_t* counts, void* stream);
 
+/* ---- plain rejection ABC: prior draw -> simulation -> distance -> the Model's own acceptance, one fused kernel (csrc/glabc_abc.hip).
+ * What picks a tolerance (a quantile of the prior-predictive distances), starts chains (the nearest draws) and samples the
+ * samplers' target independently of them (glabcmcmc_amd/rejection.py).
+ *
+ * Draw r < n has the 64-bit id  ids ? ids[r] : row0 + r.  `ids` is a DEVICE array; it may hold any order, repeats and values >= 2^32.
+ * The outputs are device arrays.  theta_out / y_out are dimension-major with stride `stride` >= n, the layout of glabc_chains:
+ *     theta_out[j * stride + r]   j < theta_dim          y_out[j * stride + r]   j < y_dim
+ * and columns n .. stride - 1 are never written; dis_out[r] (float32) and accept_out[r] (one byte, 0 or 1) are dense.  Each output
+ * may be NULL, but not all four; what only a NULL output needs is neither computed nor stored.
+ *
+ * Specification of a draw.  The result depends on (model, seed, id) only -- never on n, row0, the position in `ids` or the launch
+ * geometry -- and restates three entry points above.  With id_lo / id_hi the two words of the id:
+ *     theta  = row id of glabc_dist_forward(&model->prior, ., seed, .): the Philox blocks (seed; id_lo, id_hi, 0, b),
+ *              b < ceil(theta_dim / 4), DiagGaussian: Box-Muller pairs of words (2i, 2i + 1), Uniform: one float32 uniform per word,
+ *              theta_j = p0_j + p2_j * e_j (two rounded operations)
+ *     y      = glabc_model_simulate(model, theta, eps = NULL, seed ^ GLABC_ABC_NOISE_KEY, id): the same counters under another key,
+ *              so theta and the noise are independent
+ *     dis    = glabc_model_discrepancy(model, y)
+ *     u      = glabc_uniform_f32(word 0 of Philox(seed ^ GLABC_ABC_ACCEPT_KEY; id_lo, id_hi, 0, 0))
+ *     e      = (dis - 0.0f) / kern_scale
+ *     p      = glabc_expf(-(0.5f * (e * e)))                       K_eps(dis) / K_eps(0) of calculate_log_kernel, Mixture.py:38-45
+ *     accept = u < p ? 1 : 0
+ * every line one rounded float32 operation per operator (no FMA: -ffp-contract=off), so a NaN distance gives accept = 0.
+ *
+ * Models: GLABC_SIM_ABS_GAUSS with theta_dim == y_dim in 1 .. GLABC_MAX_DIM, and GLABC_SIM_GK (4, 8); the prior DiagGaussian or Uniform.
+ * Refusals, in this order; a refused call launches nothing and writes nothing:
+ *   a NULL model, or all four outputs NULL                                                        GLABC_ERR_NULL
+ *   theta_dim or y_dim outside 1 .. GLABC_MAX_DIM, GLABC_SIM_GK not (4, 8), GLABC_SIM_ABS_GAUSS with y_dim != theta_dim    GLABC_ERR_DIM
+ *   GLABC_SIM_USER (or an unknown kind), a prior that is not DiagGaussian / Uniform, a prior whose dim != theta_dim       GLABC_ERR_KIND
+ *   n < 0, stride < n, row0 < 0, or row0 != 0 together with ids                                    GLABC_ERR_ARG
+ * n == 0 returns GLABC_OK and writes nothing.  The parameters' values are not examined (a scale of 0 draws a constant).
+ * GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no struct changes and no existing draw moves. */
+#define GLABC_ABC_NOISE_KEY  0x9E3779B97F4A7C15ull
+#define GLABC_ABC_ACCEPT_KEY 0xD1B54A32D192ED03ull
+int glabc_abc_draws(const glabc_model* model, uint64_t seed, int64_t row0, const int64_t* ids, int64_t n, int64_t stride,
+                    float* theta_out, float* y_out, float* dis_out, uint8_t* accept_out, void* stream);
+
 /* ---- KernelDensity, the adaptive proposal of AGLMCMC (kernel_density.py:4-177) --------
  * A weighted Gaussian KDE over n_samples centres.  All arrays are device pointers; x is dimension-major.
  *
