@@ -288,18 +288,55 @@ inline int check_histogram(const float* history, int64_t n_rows, int32_t theta_d
 
 // ---- glabc_abc_draws: the Model a fused rejection draw is compiled for and the range of draws, in the order include/glabc.h lists
 // the refusals.  The parameters' values are not looked at: a draw from a prior of scale 0 or NaN is what the arithmetic says it is
-inline int check_abc_draws(const glabc_model* m, int64_t row0, const int64_t* ids, int64_t n, int64_t stride, const float* theta_out,
-                           const float* y_out, const float* dis_out, const uint8_t* accept_out)
+inline int check_abc_model(const glabc_model* m)
 {
-    if (!m || (!theta_out && !y_out && !dis_out && !accept_out)) return GLABC_ERR_NULL;
     if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
     if (m->sim_kind == GLABC_SIM_GK && (m->theta_dim != 4 || m->y_dim != 8)) return GLABC_ERR_DIM;
     if (m->sim_kind == GLABC_SIM_ABS_GAUSS && m->y_dim != m->theta_dim) return GLABC_ERR_DIM;
     if (m->sim_kind != GLABC_SIM_ABS_GAUSS && m->sim_kind != GLABC_SIM_GK) return GLABC_ERR_KIND;
     if (m->prior.kind != GLABC_DIST_DIAG_GAUSS && m->prior.kind != GLABC_DIST_UNIFORM) return GLABC_ERR_KIND;
     if (m->prior.dim != m->theta_dim) return GLABC_ERR_KIND;
-    if (n < 0 || stride < n || row0 < 0 || (ids && row0 != 0)) return GLABC_ERR_ARG;
     return GLABC_OK;
+}
+
+inline int check_abc_range(int64_t row0, const int64_t* ids, int64_t n, int64_t stride)
+{
+    return (n < 0 || stride < n || row0 < 0 || (ids && row0 != 0)) ? GLABC_ERR_ARG : GLABC_OK;
+}
+
+inline int check_abc_draws(const glabc_model* m, int64_t row0, const int64_t* ids, int64_t n, int64_t stride, const float* theta_out,
+                           const float* y_out, const float* dis_out, const uint8_t* accept_out)
+{
+    if (!m || (!theta_out && !y_out && !dis_out && !accept_out)) return GLABC_ERR_NULL;
+    if (int e = check_abc_model(m)) return e;
+    return check_abc_range(row0, ids, n, stride);
+}
+
+// ---- glabc_kde: what every entry point that reads a fitted KernelDensity asks of its descriptor (cum_q is glabc_kde_sample's and
+// glabc_smc_draws' alone and they ask for it themselves)
+inline int kde_check(const glabc_kde* k)
+{
+    if (!k) return GLABC_ERR_NULL;
+    if (k->dim < 1 || k->dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    if (k->n_samples < 1) return GLABC_ERR_ARG;
+    if (!k->x || !k->log_w) return GLABC_ERR_NULL;
+    for (int d = 0; d < k->dim; ++d)
+        if (!(k->bandwidth[d] > 0.0f) || k->bandwidth[d] == INFINITY) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
+// ---- glabc_smc_draws: check_abc_draws with a fifth output and the population between the Model and the range of draws, in the order
+// include/glabc.h lists the refusals.  The population's values are looked at (kde_check): a bandwidth of 0 has no mixture density
+inline int check_smc_draws(const glabc_model* m, const glabc_kde* pop, int64_t row0, const int64_t* ids, int64_t n, int64_t stride,
+                           const float* theta_out, const float* y_out, const float* dis_out, const float* log_prior_out,
+                           const uint8_t* accept_out)
+{
+    if (!m || !pop || (!theta_out && !y_out && !dis_out && !log_prior_out && !accept_out)) return GLABC_ERR_NULL;
+    if (int e = check_abc_model(m)) return e;
+    if (int e = kde_check(pop)) return e;
+    if (!pop->cum_q) return GLABC_ERR_NULL;
+    if (pop->dim != m->theta_dim) return GLABC_ERR_DIM;
+    return check_abc_range(row0, ids, n, stride);
 }
 
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------

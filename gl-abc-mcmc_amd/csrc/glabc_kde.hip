@@ -5,6 +5,7 @@
 //                         sum of exp) so that the sum can be taken exactly in fixed point -> independent of the lane
 //                         split, bit-identical to the scalar checker
 //   kde_sample_kernel     one thread per draw: inverse-CDF index on the integer prefix sums + bandwidth * normal
+//                         (kde_draw_row of glabc_kde_draw.h, which glabc_smc_draws calls too)
 //
 // The O(points x centres) log_prob is the only heavy piece: per pair D subtract/divide/square, 4 adds and -- in the
 // second pass -- one exp.  Centres are read coalesced (dimension-major) and are shared by every wavefront, so after the
@@ -15,8 +16,10 @@
 
 #include "../../include/glabc.h"
 #include "../../include/glabc_numerics.h"
+#include "glabc_check.h"
 #include "glabc_device.h"
 #include "glabc_dispatch.h"
+#include "glabc_kde_draw.h"
 #include "glabc_launch.h"
 
 using namespace glabc;
@@ -206,41 +209,10 @@ __global__ void __launch_bounds__(256) kde_sample_kernel(const KdeArgs<D> a)
 {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= a.n_points) return;
-    const uint64_t gid = (uint64_t)(a.row0 + r);
-    constexpr int NB = (D + 2 + 3) / 4;
-    float nrm[4 * NB];
-    double u = 0.0;
+    float z[D];
+    kde_draw_row<D>(a.x, a.cum_q, a.n_samples, a.bw, (uint64_t)(a.row0 + r), a.seed_lo, a.seed_hi, z);        // glabc_kde_draw.h
 #pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        glabc_u32x4 w = glabc_philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), 0u, (uint32_t)b, a.seed_lo, a.seed_hi);
-        if (b == 0) {
-            u = glabc_uniform_f64(w.v[0], w.v[1]);
-            glabc_normal_pair(w.v[2], w.v[3], &nrm[0], &nrm[1]);
-        } else {
-            glabc_normal_pair(w.v[0], w.v[1], &nrm[4 * b - 2], &nrm[4 * b - 1]);
-            glabc_normal_pair(w.v[2], w.v[3], &nrm[4 * b], &nrm[4 * b + 1]);
-        }
-    }
-    const int64_t S = a.n_samples;
-    const int64_t target = (int64_t)(u * (double)a.cum_q[S - 1]);
-    int64_t lo = 0, hi = S - 1;                            // first j with cum_q[j] > target (clamped to S-1)
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.cum_q[mid] > target) hi = mid; else lo = mid + 1;
-    }
-#pragma unroll
-    for (int d = 0; d < D; ++d) a.out[d * a.n_points + r] = a.x[d * S + lo] + nrm[d] * a.bw[d];   // kernel_density.py:147-148
-}
-
-int kde_check(const glabc_kde* k)
-{
-    if (!k) return GLABC_ERR_NULL;
-    if (k->dim < 1 || k->dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
-    if (k->n_samples < 1) return GLABC_ERR_ARG;
-    if (!k->x || !k->log_w) return GLABC_ERR_NULL;
-    for (int d = 0; d < k->dim; ++d)
-        if (!(k->bandwidth[d] > 0.0f) || k->bandwidth[d] == __builtin_inff()) return GLABC_ERR_ARG;
-    return GLABC_OK;
+    for (int d = 0; d < D; ++d) a.out[d * a.n_points + r] = z[d];
 }
 
 template <int D>

@@ -1,0 +1,370 @@
+"""smc -- ABC-SMC (population Monte Carlo): weighted particles that walk a ladder of tolerances down to the samplers' target.
+
+Rejection from the prior (``rejection``) pays 1 / acceptance rate simulations per kept draw, and the rate collapses when the
+prior is wide or epsilon small.  ABC-SMC proposes from the previous generation instead: pick an ancestor by weight, perturb it
+with a Gaussian kernel (a weighted KDE of the population, ``glabc_kde_fit``), keep the proposal if its distance is within this
+generation's tolerance, and weigh it by prior density / proposal density (Beaumont et al. 2009).
+
+Generations.  Generation 0 is ``rejection.sample(kernel="hard", n_accept=N)`` over ceil(N / quantile) prior draws, uniform
+weights.  Generation t >= 1 has the tolerance max(epsilon_stop, the order statistic of rank floor(quantile (N - 1)) of the
+previous distances), or the next entry of the ladder ``epsilons`` (its entries are the tolerances of generations 1, 2, ...; the
+last one is epsilon_stop).  The generation that reaches epsilon_stop is the last hard one.  With ``kernel="model"`` one more
+generation follows: it proposes from the last hard population and accepts with probability K_eps(distance) / K_eps(0) at
+``ABCset.epsilon`` -- the Model's own kernel --, so its weighted particles target exactly the posterior the MCMC samplers target.
+
+Fused path.  ``glabc_smc_draws`` (include/glabc.h, csrc/glabc_smc.hip) does ancestor -> perturbation -> prior density ->
+simulation -> distance -> acceptance in registers; a draw is a pure function of (Model, population, key, 64-bit id).  A
+generation sweeps ids 0, 1, 2, ... in launches that ask for the distance alone (4 bytes per draw; the acceptance byte alone in
+the soft generation), sized from the acceptance rate seen so far; ``torch.nonzero`` finds the kept ids, the sweep stops once N
+are kept, and the FIRST N BY ID are the generation: the result depends on (Model, N, settings, seed), never on how the sweep was
+cut.  One ``glabc_smc_draws(ids=...)`` call regenerates theta, y, distance and log-prior of the kept draws.  A proposal of prior
+density 0 has the distance +inf and is never kept.  Generation t runs under the key (seed + t * 0x632BE59BD9B4E019) mod 2^64.
+There is no CPU implementation of this path.
+
+Generic path (``path="generic"``): plain torch on the Model's callbacks and on ``prior`` (``forward`` and ``log_prob``), for
+``CompiledModel``, Gamma priors and callback Models, CPU tensors included.  Ancestors come from ``torch.multinomial``, the
+perturbation from ``torch.randn`` (torch's global generator), the mixture density is a chunked float64 ``logsumexp``; ids are
+draw positions.  Ladder, selection and weights are the code the fused path runs.
+
+Weights: log w = log prior(theta) - log q(theta), q the proposal mixture, normalised in float64.  ess = 1 / sum w^2.
+"""
+import ctypes as C
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _capi, engine, rejection
+from .kernel_density import KernelDensity
+
+SEED_STEP = 0x632BE59BD9B4E019    # generation t draws under the key (seed + t * SEED_STEP) mod 2^64
+MIN_LAUNCH = 1 << 14              # draws per launch of a sweep, at least (at most rejection.MAX_LAUNCH)
+HEADROOM = 1.25                   # a launch is sized for the particles still missing / the rate seen, times this
+LOGQ_ELEMENTS = 1 << 24           # points x centres per chunk of the generic path's mixture density
+OUTPUTS = ("theta", "y", "distance", "log_prior", "accept")
+
+Population = namedtuple("Population", "theta y distance weights epsilon ess generations")
+Draws = namedtuple("Draws", "theta y distance log_prior accept")
+
+
+# ---------------------------------------------------------------------------------- glabc_smc_draws
+def _launch(desc, kde, seed, row0, ids, n, dev, want):
+    """glabc_smc_draws -> the dimension-major buffers {name: tensor} of the wanted outputs"""
+    shapes = {"theta": (desc.theta_dim, n), "y": (desc.y_dim, n), "distance": (n,), "log_prior": (n,), "accept": (n,)}
+    out = {name: torch.empty(shapes[name], dtype=torch.uint8 if name == "accept" else torch.float32, device=dev) for name in want}
+    ptr = lambda name: out[name].data_ptr() if name in out and n else None          # noqa: E731
+    if n:
+        with torch.cuda.device(dev):
+            _capi.check(_capi.lib().glabc_smc_draws(C.byref(desc), C.byref(kde.descriptor()), seed, row0,
+                                                    None if ids is None else ids.data_ptr(), n, n, ptr("theta"), ptr("y"), ptr("distance"),
+                                                    ptr("log_prior"), ptr("accept"),
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "glabc_smc_draws")
+    return out
+
+
+def draws(ABCset, population, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, device=None):
+    """``glabc_smc_draws`` on device tensors -> Draws(theta (n, D), y (n, YD), distance (n,), log_prior (n,), accept (n,) uint8),
+    None for what `want` leaves out; theta and y are views of the kernel's dimension-major buffers.  `population` is a fitted
+    ``KernelDensity`` of theta_dim features.  Draw r has id ``ids[r]`` (any integers in 0 .. 2^63 - 1, any order, repeats allowed;
+    `n` must be their number) or ``row0 + r``; a draw depends on (Model, population, seed, id) only.  The distance of a proposal
+    of prior density 0 is +inf."""
+    n = rejection._count("n", n, 0)
+    row0 = rejection._count("row0", row0, 0)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in OUTPUTS for w in want):
+        raise ValueError("want names one or more of %r, got %r" % (OUTPUTS, want))
+    if seed is None or isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError("seed must be an integer, got %r" % (seed,))
+    desc = rejection.accepted(ABCset, rejection._epsilon(ABCset, epsilon, True))
+    if desc is None:
+        raise ValueError("glabc_smc_draws does not take this Model (%s): use sample(path=\"generic\")" % type(ABCset).__name__)
+    if not isinstance(population, KernelDensity) or not population._fitted:
+        raise ValueError("population must be a fitted KernelDensity, got %r" % (population,))
+    if population.dim != desc.theta_dim:
+        raise ValueError("population has %d features, the Model %d parameters" % (population.dim, desc.theta_dim))
+    if ids is not None:
+        if row0 != 0:
+            raise ValueError("row0 must be 0 when ids are given, got %r" % (row0,))
+        ids = torch.as_tensor(ids)
+        if ids.dim() != 1 or ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.numel() != n:
+            raise ValueError("ids are n = %d integers, got shape %r of %s" % (n, tuple(ids.shape), ids.dtype))
+        if n and int(ids.min()) < 0:
+            raise ValueError("ids must be >= 0, got %d" % int(ids.min()))
+    dev = engine.require_device(device)
+    if population.device != dev:
+        raise ValueError("population lives on %s, the draws on %s" % (population.device, dev))
+    if ids is not None:
+        ids = ids.to(device=dev, dtype=torch.int64).contiguous()
+    out = _launch(desc, population, engine.draw_seed(seed), row0, ids, n, dev, want)
+    return Draws(out["theta"].t() if "theta" in out else None, out["y"].t() if "y" in out else None, out.get("distance"),
+                 out.get("log_prior"), out.get("accept"))
+
+
+# ---------------------------------------------------------------------------------- arguments
+def _number(name, value, low_open, high=None):
+    """a finite float > low_open (and <= high)"""
+    ok = isinstance(value, (int, float, np.floating, np.integer)) and not isinstance(value, bool)
+    v = float(value) if ok else math.nan
+    if not (math.isfinite(v) and v > low_open and (high is None or v <= high)):
+        raise ValueError("%s must be a number in (%g, %s], got %r" % (name, low_open, "inf)" if high is None else "%g" % high, value))
+    return v
+
+
+def _ladder(epsilons):
+    try:
+        lad = [float(e) for e in epsilons]
+    except (TypeError, ValueError):
+        raise ValueError("epsilons must be a sequence of numbers, got %r" % (epsilons,)) from None
+    if not lad or any(not math.isfinite(e) or e <= 0.0 for e in lad):
+        raise ValueError("epsilons must be positive finite numbers, at least one, got %r" % (epsilons,))
+    if any(b >= a for a, b in zip(lad, lad[1:])):
+        raise ValueError("epsilons must be strictly decreasing, got %r" % (lad,))
+    return [float(np.float32(e)) for e in lad]
+
+
+def _bandwidth(bandwidth, dim):
+    """-> a rule's name, or the fixed bandwidth as a list of `dim` floats"""
+    if isinstance(bandwidth, str):
+        if bandwidth not in ("silverman", "scott", "beaumont"):
+            raise ValueError('bandwidth is "silverman", "scott", "beaumont", a float or a tensor, got %r' % (bandwidth,))
+        return bandwidth
+    try:
+        bw = torch.as_tensor(bandwidth, dtype=torch.float32).detach().cpu().reshape(-1)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError('bandwidth is "silverman", "scott", "beaumont", a float or a tensor, got %r' % (bandwidth,)) from None
+    if bw.numel() not in (1, dim) or not bool((torch.isfinite(bw) & (bw > 0)).all()):
+        raise ValueError("a fixed bandwidth is 1 or %d positive finite numbers, got %r" % (dim, bandwidth))
+    return [float(v) for v in bw.expand(dim)]
+
+
+def rule_factor(rule, n, dim):
+    """the factor h of bandwidth = h * weighted std: Silverman's and Scott's rules as KernelDensity has them, and sqrt(2) --
+    a kernel of twice the weighted variance -- of Beaumont et al. 2009"""
+    if rule == "silverman":
+        return (n * (dim + 2) / 4.) ** (-1. / (dim + 4))
+    if rule == "scott":
+        return n ** (-1. / (dim + 4))
+    return math.sqrt(2.0)
+
+
+def _generation_key(seed0, t):
+    return (seed0 + t * SEED_STEP) & 0xFFFFFFFFFFFFFFFF
+
+
+def _launch_size(need, rate, start, max_draws):
+    """draws of the next launch: the particles still missing over the rate seen, with headroom, inside the limits"""
+    k = int(math.ceil(HEADROOM * need / max(rate, 1e-12)))
+    return max(0, min(max(k, MIN_LAUNCH), rejection.MAX_LAUNCH, max_draws - start))
+
+
+def _ladder_text(gens):
+    return ", ".join("%.6g" % g["epsilon"] for g in gens)
+
+
+def _check_bandwidth(bw):
+    bad = [j for j, v in enumerate(bw) if not (math.isfinite(v) and v > 0.0)]
+    if bad:
+        raise RuntimeError("the population is degenerate: the bandwidth of coordinate %d is %r (every particle has the same value there?)"
+                           % (bad[0], bw[bad[0]]))
+
+
+def _normalise(log_w):
+    """float64 weights summing to 1 of float64 log-weights, and the effective sample size 1 / sum w^2"""
+    w = torch.softmax(log_w, dim=0)
+    return w, float(1.0 / (w * w).sum())
+
+
+# ---------------------------------------------------------------------------------- one generation, fused
+class _Rule(KernelDensity):
+    """KernelDensity whose rule factor is this module's (the two rules of the class and Beaumont's)"""
+
+    def _rule_factor(self, n):
+        return rule_factor(self.bandwidth, n, self.dim)
+
+
+class _Fused:
+    def __init__(self, desc, dev, seed):
+        self.desc, self.dev = desc, dev
+        self.seed0 = engine.draw_seed(seed)
+
+    def first(self, n_draws, N):
+        r = rejection._fused(self.desc, n_draws, "hard", None, N - 1, N, _generation_key(self.seed0, 0), self.dev)
+        return r.theta, r.y, r.distance, r.epsilon
+
+    def rank(self, dis, rank):
+        return rejection._select_rank(dis, rank)
+
+    def fit(self, theta, weights, bandwidth):
+        kde = _Rule(bandwidth, device=self.dev).fit(theta, weights.to(torch.float32))
+        bw = kde._consts[:kde.dim]
+        _check_bandwidth(bw)
+        return kde, bw
+
+    def generation(self, t, kde, N, eps, rate, max_draws):
+        """the first N draws by id that are kept (eps None: by the Model's kernel) -> theta, y, distance, log w, n_draws"""
+        name = "accept" if eps is None else "distance"
+        key = _generation_key(self.seed0, t)
+        kept, n_kept, start = [], 0, 0
+        while n_kept < N:
+            k = _launch_size(N - n_kept, rate, start, max_draws)
+            if k == 0:
+                raise RuntimeError("generation %d kept %d of the %d particles in max_draws = %d draws (acceptance rate %.3g)"
+                                   % (t, n_kept, N, max_draws, n_kept / max(start, 1)))
+            buf = _launch(self.desc, kde, key, start, None, k, self.dev, (name,))[name]
+            ids = torch.nonzero(buf if eps is None else buf <= eps).view(-1) + start
+            kept.append(ids)
+            n_kept += ids.numel()
+            start += k
+            rate = max(n_kept, 1) / start
+        ids = torch.cat(kept)[:N]
+        out = _launch(self.desc, kde, key, 0, ids, N, self.dev, ("theta", "y", "distance", "log_prior"))
+        log_q = kde.log_prob_soa(out["theta"])
+        log_w = out["log_prior"].double() - log_q.double()
+        return out["theta"].t(), out["y"].t(), out["distance"], log_w, int(ids[-1]) + 1
+
+
+# ---------------------------------------------------------------------------------- one generation, plain torch
+class _Mixture:
+    """the proposal of the generic path: centres x (S, D), weights (S,) float64, bandwidth (D,)"""
+
+    def __init__(self, x, weights, bw):
+        self.x, self.w, self.bw = x, weights, torch.tensor(bw, dtype=torch.float32, device=x.device)
+
+    def sample(self, n):
+        j = torch.multinomial(self.w, n, replacement=True)
+        return self.x[j] + torch.randn(n, self.x.shape[1], device=self.x.device) * self.bw
+
+    def log_prob(self, theta):
+        x, bw = self.x.double(), self.bw.double()
+        const = torch.log(self.w) - torch.log(bw).sum() - 0.5 * x.shape[1] * math.log(2.0 * math.pi)
+        out = []
+        step = max(1, LOGQ_ELEMENTS // x.shape[0])
+        for first in range(0, theta.shape[0], step):
+            e = (theta[first:first + step].double().unsqueeze(1) - x.unsqueeze(0)) / bw
+            out.append(torch.logsumexp(const - 0.5 * (e * e).sum(dim=2), dim=1))
+        return torch.cat(out) if out else torch.empty(0, dtype=torch.float64, device=theta.device)
+
+
+class _Generic:
+    def __init__(self, ABCset, prior, model_eps):
+        self.ABCset, self.prior, self.model_eps = ABCset, prior, model_eps
+
+    def first(self, n_draws, N):
+        r = rejection._generic(self.ABCset, self.prior, n_draws, "hard", None, N - 1, N)
+        return r.theta, r.y, r.distance, r.epsilon
+
+    def rank(self, dis, rank):
+        return float(torch.kthvalue(dis, rank + 1).values)
+
+    def fit(self, theta, weights, bandwidth):
+        if isinstance(bandwidth, str):                            # the rule factor times the weighted std (unbiased, as glabc_kde_fit)
+            x = theta.double()
+            mean = (weights.unsqueeze(1) * x).sum(dim=0)
+            var = (weights.unsqueeze(1) * (x - mean) ** 2).sum(dim=0) / max(1.0 - float((weights * weights).sum()), 1e-10)
+            bw = [float(v) for v in rule_factor(bandwidth, theta.shape[0], theta.shape[1]) * var.sqrt()]
+        else:
+            bw = list(bandwidth)
+        _check_bandwidth(bw)
+        return _Mixture(theta, weights.to(theta.device), bw), bw
+
+    def generation(self, t, mix, N, eps, rate, max_draws):
+        A = self.ABCset
+        rows, n_kept, start, last = [], 0, 0, -1
+        while n_kept < N:
+            k = min(_launch_size(N - n_kept, rate, start, max_draws), rejection.GENERIC_CHUNK)
+            if k == 0:
+                raise RuntimeError("generation %d kept %d of the %d particles in max_draws = %d draws (acceptance rate %.3g)"
+                                   % (t, n_kept, N, max_draws, n_kept / max(start, 1)))
+            theta = mix.sample(k)
+            lp = self.prior.log_prob(theta).reshape(k).to(torch.float32)
+            y = A.generate_samples(theta, 1).reshape(k, -1)
+            d = A.discrepancy(y).reshape(k).to(torch.float32)
+            d = torch.where(lp == -math.inf, torch.full_like(d, math.inf), d)
+            if eps is None:
+                log_k = lambda x: A.calculate_log_kernel_dis(x, self.model_eps).reshape(-1)          # noqa: E731
+                p = torch.exp(log_k(d) - log_k(torch.zeros(1, dtype=d.dtype, device=d.device)))
+                mask = torch.rand(k, device=d.device) < p.to(d.device)
+            else:
+                mask = d <= eps
+            i = torch.nonzero(mask).view(-1)[:N - n_kept]
+            if i.numel():
+                rows.append((theta[i], y[i], d[i], lp[i]))
+                last = start + int(i[-1])
+            n_kept += i.numel()
+            start += k
+            rate = max(n_kept, 1) / start
+        theta, y, d, lp = (torch.cat(c) for c in zip(*rows))
+        return theta, y, d, lp.double() - mix.log_prob(theta), last + 1
+
+
+# ---------------------------------------------------------------------------------- the generations
+def sample(ABCset, n_particles, *, kernel="model", epsilon=None, epsilons=None, quantile=0.5, bandwidth="silverman", max_generations=30,
+           max_draws=1 << 30, seed=None, device=None, path="auto", prior=None):
+    """ABC-SMC -> Population(theta (N, D), y (N, YD), distance (N,), weights (N,) float64 summing to 1, epsilon, ess, generations).
+    kernel="model": hard generations down to `epsilon` (default 3 ``ABCset.epsilon``), then one accepted by the Model's own kernel
+    at ``ABCset.epsilon``; kernel="hard": hard generations down to `epsilon`, or along the ladder `epsilons` (module docstring).
+    bandwidth: "silverman" (default) / "scott": the rule's factor times the weighted std; "beaumont": sqrt(2) times it; a float or
+    a tensor: fixed.  `generations` holds one dict per generation: epsilon, kernel, n_draws, rate, ess, bandwidth.
+    max_draws bounds the draws of one generation.  path: as in ``rejection.sample`` ("generic" needs ``prior=`` with forward and
+    log_prob)."""
+    N = rejection._count("n_particles", n_particles, 2)
+    max_generations = rejection._count("max_generations", max_generations, 1)
+    max_draws = rejection._count("max_draws", max_draws, 1)
+    q = _number("quantile", quantile, 0.0, 1.0)
+    if kernel not in ("model", "hard"):
+        raise ValueError('kernel is "model" or "hard", got %r' % (kernel,))
+    if epsilon is not None and epsilons is not None:
+        raise ValueError("give epsilon or the ladder epsilons, not both: got epsilon=%r, epsilons=%r" % (epsilon, epsilons))
+    ladder = None if epsilons is None else _ladder(epsilons)
+    model_eps = rejection._epsilon(ABCset, None, True) if kernel == "model" else None
+    if ladder is not None:
+        eps_stop = ladder[-1]
+    elif epsilon is not None:
+        eps_stop = float(np.float32(_number("epsilon", epsilon, 0.0)))
+    elif kernel == "model":
+        eps_stop = float(np.float32(3.0 * model_eps))
+    else:
+        raise ValueError('kernel="hard" needs epsilon or the ladder epsilons')
+    dim = getattr(ABCset, "theta_dim", None)
+    desc = rejection._path(ABCset, path, model_eps)
+    bandwidth = _bandwidth(bandwidth, int(dim) if dim is not None else (desc.theta_dim if desc is not None else 1))
+    if desc is None:
+        if prior is None or not callable(getattr(prior, "forward", None)) or not callable(getattr(prior, "log_prob", None)):
+            raise ValueError('path="generic" needs prior=, a distribution object with forward(n) and log_prob(theta), got %r' % (prior,))
+        run = _Generic(ABCset, prior, model_eps)
+    else:
+        run = _Fused(desc, engine.require_device(device), seed)
+
+    n0 = int(math.ceil(N / q))
+    theta, y, dis, eps = run.first(n0, N)
+    weights = torch.full((N,), 1.0 / N, dtype=torch.float64, device=theta.device)
+    ess, rate = float(N), N / n0
+    gens = [dict(epsilon=eps, kernel="hard", n_draws=n0, rate=rate, ess=ess, bandwidth=None)]
+
+    def advance(t, eps_t):
+        if t > max_generations:
+            raise RuntimeError("max_generations = %d reached above epsilon = %g; the ladder so far: %s" % (max_generations, eps_stop, _ladder_text(gens)))
+        proposal, bw = run.fit(theta, weights, bandwidth)
+        th, yy, d, log_w, n_draws = run.generation(t, proposal, N, eps_t, gens[-1]["rate"], max_draws)
+        w, e = _normalise(log_w)
+        gens.append(dict(epsilon=model_eps if eps_t is None else eps_t, kernel="model" if eps_t is None else "hard", n_draws=n_draws,
+                         rate=N / n_draws, ess=e, bandwidth=bw))
+        return th, yy, d, w, e
+
+    t = 0
+    while eps > eps_stop:
+        t += 1
+        if ladder is not None:
+            eps_t = ladder[t - 1]
+        else:
+            eps_t = max(eps_stop, float(np.float32(run.rank(dis, int(math.floor(q * (N - 1)))))))
+        if not eps_t < eps:
+            raise RuntimeError("the tolerance of generation %d, %g, does not decrease before epsilon = %g; the ladder so far: %s"
+                               % (t, eps_t, eps_stop, _ladder_text(gens)))
+        theta, y, dis, weights, ess = advance(t, eps_t)
+        eps = eps_t
+    if kernel == "model":
+        theta, y, dis, weights, ess = advance(t + 1, None)
+        eps = model_eps
+    return Population(theta, y, dis, weights, eps, ess, gens)

@@ -855,6 +855,41 @@ int glabc_kde_log_prob_indexed(const glabc_kde* kde, const float* pts, int64_t s
  * words 2-3 of block 0, then blocks 1..).  out is dimension-major [dim][n]. */
 int glabc_kde_sample(const glabc_kde* kde, int64_t n, uint64_t seed, int64_t row0, float* out, void* stream);
 
+/* ---- ABC-SMC proposals: ancestor -> perturbation -> prior density -> simulation -> distance -> acceptance, one fused kernel
+ * (csrc/glabc_smc.hip).  glabc_abc_draws with theta drawn from a fitted population -- the weighted particles of the previous
+ * generation as a glabc_kde -- instead of the prior; the generations, tolerances and weights are glabcmcmc_amd/smc.py's.
+ *
+ * Ids, layouts and NULL outputs are glabc_abc_draws': draw r < n has the 64-bit id  ids ? ids[r] : row0 + r  (`ids` a DEVICE array, any
+ * order, repeats, values >= 2^32); theta_out / y_out are dimension-major with stride `stride` >= n and columns n .. stride - 1 are never
+ * written; dis_out[r], log_prior_out[r] (float32) and accept_out[r] (one byte, 0 or 1) are dense.  Each output may be NULL, but not all
+ * five; what only a NULL output needs is neither computed nor stored.  More than 2^30 draws go in several launches; every index is
+ * 64 bits wide.
+ *
+ * Specification of a draw.  The result depends on (model, population, seed, id) only, and restates entry points of this header:
+ *     theta     = row id of glabc_kde_sample(population, ., seed, .): the Philox blocks (seed; id_lo, id_hi, 0, b), b < ceil((dim + 2) / 4);
+ *                 words 0-1 of block 0 give the float64 uniform u, the ancestor is the first j with
+ *                 cum_q[j] > (int64)(u * cum_q[n_samples - 1]), the normals come from words 2-3 of block 0 and then from blocks 1
+ *                 onwards, theta_d = x[d * n_samples + j] + nrm_d * bandwidth_d (two rounded operations)
+ *     log_prior = glabc_model_prior_log_prob(model, theta)
+ *     y         = glabc_model_simulate(model, theta, eps = NULL, seed ^ GLABC_ABC_NOISE_KEY, id)
+ *     dis       = glabc_model_discrepancy(model, y), replaced by +inf where log_prior == -inf (a select: y_out still holds the simulated
+ *                 row).  A proposal outside a Uniform prior's support is then kept by neither acceptance rule
+ *     accept    = as in glabc_abc_draws on that dis, under seed ^ GLABC_ABC_ACCEPT_KEY (dis = +inf: p = 0, accept = 0)
+ *
+ * Models: those of glabc_abc_draws.  Refusals, in this order; a refused call launches nothing and writes nothing:
+ *   a NULL model or population, or all five outputs NULL                                          GLABC_ERR_NULL
+ *   the Model's dimensions, then its kinds, as glabc_abc_draws refuses them                       GLABC_ERR_DIM, GLABC_ERR_KIND
+ *   the population as glabc_kde_sample refuses it: dim outside 1 .. GLABC_MAX_DIM (GLABC_ERR_DIM), n_samples < 1 (GLABC_ERR_ARG),
+ *     a NULL x or log_w (GLABC_ERR_NULL), a bandwidth that is not positive and finite (GLABC_ERR_ARG); then
+ *     a NULL cum_q                                                                                GLABC_ERR_NULL
+ *     population->dim != theta_dim                                                                GLABC_ERR_DIM
+ *   n < 0, stride < n, row0 < 0, or row0 != 0 together with ids                                    GLABC_ERR_ARG
+ * n == 0 returns GLABC_OK and writes nothing.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no struct changes and no existing
+ * draw moves. */
+int glabc_smc_draws(const glabc_model* model, const glabc_kde* population, uint64_t seed, int64_t row0, const int64_t* ids,
+                    int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out, float* log_prior_out,
+                    uint8_t* accept_out, void* stream);
+
 /* AGLMCMC.py:199-204 (and :104-109): weights of a proposal pool from its stored discrepancies,
  * w[r] = exp((prior(theta_r) + calculate_log_kernel_dis(dis_r)) - log_q[r]), NaN -> 0.  The threshold is the one in
  * model->kern_* (the caller passes a copy of its descriptor with the annealed eps_hat, Mixture.py:47-53).
