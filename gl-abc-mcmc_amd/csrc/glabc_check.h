@@ -397,4 +397,26 @@ inline int check_rtc_mix_run(const RtcShape& p, bool mix_program, const glabc_mo
     return check_step_counter(r);
 }
 
+// ---- glabc_rtc_abc_draws / glabc_rtc_smc_draws: a launch of the run-time compiled DRAWS program of shape `p` -------------------------
+// draws_program: the program was built from the draws table (glabc_rtc_compile_draws, glabc_rtc_draws_kernels.h); no other program
+// holds a draw kernel.  any_output: one of the entry point's outputs is not NULL.  smc: glabc_rtc_smc_draws, which reads `pop` --
+// refused as glabc_smc_draws refuses it (kde_check, cum_q, the dimension), between the Model and the range of draws; the range is
+// check_abc_range's.  The order is the contract (include/glabc.h); the entry point has refused a NULL program before.
+inline int check_rtc_draws(const RtcShape& p, bool draws_program, const glabc_model* m, bool smc, const glabc_kde* pop, bool any_output,
+                           int64_t row0, const int64_t* ids, int64_t n, int64_t stride)
+{
+    if (!m || !any_output) return GLABC_ERR_NULL;
+    if (m->sim_kind != GLABC_SIM_USER) return GLABC_ERR_KIND;
+    if (!draws_program) return GLABC_ERR_KIND;
+    if (m->theta_dim != p.theta_dim || m->y_dim != p.y_dim || m->noise.dim != p.noise_dim) return GLABC_ERR_DIM;
+    if (m->prior.kind != GLABC_DIST_DIAG_GAUSS && m->prior.kind != GLABC_DIST_UNIFORM) return GLABC_ERR_KIND;
+    if (m->prior.dim != m->theta_dim) return GLABC_ERR_KIND;
+    if (smc) {
+        if (int e = kde_check(pop)) return e;
+        if (!pop->cum_q) return GLABC_ERR_NULL;
+        if (pop->dim != m->theta_dim) return GLABC_ERR_DIM;
+    }
+    return check_abc_range(row0, ids, n, stride);
+}
+
 }  // namespace glabc

@@ -23,13 +23,24 @@
 // GLABC_RTC_WITH_MIX (glabc_rtc_compile_mix / glabc_rtc_compile_wide_mix) instantiates the GaussianMixture variant INSTEAD of the kernels
 // above: sampler_kernel<.., 1, VAR_MIX, 0> (one lane per chain whatever GLABC_RTC_L is: chain_step asserts it), or, with
 // GLABC_RTC_WIDE, wide_kernel<.., false, true> at the four lane counts.  Their argument block is a MixStepArgs (glabc_device.h).
+//
+// GLABC_RTC_DRAWS (glabc_rtc_compile_draws) instantiates no sampler at all: abc_draws_kernel (glabc_abc.h) and smc_draws_kernel
+// (glabc_smc.h), the templates glabc_abc_draws and glabc_smc_draws are instantiated from, with the user's function where the built-in
+// simulators are.  GLABC_RTC_ALGO / _N / _L are not defined for such a program.
 #pragma once
 
 #include "glabc_sampler.h"
 
 namespace glabc {
 
-#if defined(GLABC_RTC_WIDE) && defined(GLABC_RTC_WITH_MIX)
+#if defined(GLABC_RTC_DRAWS)
+}  // namespace glabc
+#include "glabc_abc.h"
+#include "glabc_smc.h"
+namespace glabc {
+template __global__ void abc_draws_kernel<GLABC_RTC_D, GLABC_RTC_YD>(const AbcArgs<GLABC_RTC_D, GLABC_RTC_YD>);
+template __global__ void smc_draws_kernel<GLABC_RTC_D, GLABC_RTC_YD>(const SmcArgs<GLABC_RTC_D, GLABC_RTC_YD>);
+#elif defined(GLABC_RTC_WIDE) && defined(GLABC_RTC_WITH_MIX)
 }  // namespace glabc
 #include "glabc_wide.h"
 namespace glabc {

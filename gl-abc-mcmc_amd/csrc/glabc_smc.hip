@@ -1,145 +1,24 @@
 // glabc_smc.hip -- ABC-SMC proposals: glabc_smc_draws of include/glabc.h, which holds the specification of a draw.
 //
-// smc_draws_kernel<D, YD> is abc_draws_kernel (glabc_abc.hip) with theta from a fitted population instead of the prior.  One lane owns
-// one draw and keeps it in registers from the ancestor to the distance: theta through kde_draw_row (glabc_kde_draw.h, what
-// glabc_kde_sample's kernel draws with), the prior's log-density through dist_log_prob, y through model_simulate and the distance
-// through model_discrepancy_rows of glabc_device.h -- the functions the row-wise entry points inline, which is what makes the bits
-// agree with their composition.  A proposal of prior density 0 gets the distance +inf by a select, so neither acceptance rule keeps
-// it and a distance-only sweep still writes 4 bytes per draw.
-// What is read from memory: the id (when the caller lists ids), log2(S) + 1 words of cum_q in the ancestor search and the D
-// coordinates of the ancestor.  The search is in global memory: cum_q is 8 S bytes and every lane reads it, so it sits in L2.
-// Which outputs are wanted is wave-uniform (a NULL pointer in the argument block): what only a NULL output needs is skipped on a
-// scalar branch.  Every index is 64 bits wide.  The by-value argument arrays are indexed by unrolled loop counters only
-// (profiles/smc_kernel_resources.txt).  Geometry: workgroups of 256 lanes, one draw per lane.
+// The kernel, smc_draws_kernel<D, YD>, lives in glabc_smc.h (a run-time compiled draws program instantiates it too, glabc_rtc.hip);
+// this file holds its nine built-in instantiations -- |theta| + noise at theta_dim 1 .. 8 and g-and-k --, the launcher and the entry point.
 #include <hip/hip_runtime.h>
 
-#include <cstddef>
 #include <cstdint>
-#include <cstring>
 
 #include "glabc_check.h"
-#include "glabc_device.h"
 #include "glabc_dispatch.h"
-#include "glabc_kde_draw.h"
+#include "glabc_draws_pack.h"
 #include "glabc_launch.h"
-#include "glabc_pack.h"
+#include "glabc_smc.h"
 
 namespace glabc {
-
-constexpr int SMC_BLOCK = 256;
-constexpr int64_t SMC_MAX_LAUNCH = (int64_t)1 << 30;          // draws per launch: the grid stays far inside 32 bits
-
-template <int D, int YD>
-struct SmcArgs {
-    StepArgs<D, YD> s;            // the Model as the samplers' kernels see it: prior, simulator, y_obs, kern_scale
-    const float* x;               // the population: centres [D][S], inclusive integer prefix sums of the weights, bandwidth
-    const int64_t* cum_q;
-    int64_t S;
-    float bw[D];
-    const int64_t* ids;           // NULL: draw r has id row0 + r
-    int64_t row0, first, n, stride;                             // this launch covers draws first .. n - 1
-    uint32_t prop_lo, prop_hi, noise_lo, noise_hi, accept_lo, accept_hi;        // the three Philox keys
-    float* theta;
-    float* y;
-    float* dis;
-    float* log_prior;
-    uint8_t* accept;
-};
-
-// The Model block of the kernel's argument, read where it is used.  The compiler loads a by-value argument in the entry block and sinks
-// the loads no further than the head of the ancestor search's loop: at D = 7 and 8 the prior, the noise and y_obs then live in scalar
-// registers across the loop, past the 102 a wavefront has (8 spilled, seven wavefronts per SIMD).  Behind a pointer the compiler
-// cannot see through, the loads are emitted after the loop.  `s` is the first member of the only argument: offset 0 of the segment
-template <int D, int YD>
-GLABC_DEV const StepArgs<D, YD>& model_after_search(const SmcArgs<D, YD>& a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    using Args = SmcArgs<D, YD>;
-    static_assert(__builtin_offsetof(Args, s) == 0, "the Model block leads the argument");
-    auto p = __builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return *(const StepArgs<D, YD>*)p;
-#else
-    return a.s;
-#endif
-}
-
-template <int D, int YD>
-__global__ void __launch_bounds__(SMC_BLOCK) smc_draws_kernel(const SmcArgs<D, YD> a)
-{
-    const int64_t r = a.first + (int64_t)blockIdx.x * SMC_BLOCK + threadIdx.x;
-    if (r >= a.n) return;
-    const uint64_t id = (uint64_t)(a.ids ? a.ids[r] : a.row0 + r);
-    const uint32_t id_lo = (uint32_t)id, id_hi = (uint32_t)(id >> 32);
-
-    // theta: row id of glabc_kde_sample(population), through the function its kernel draws with (glabc_kde_draw.h)
-    float theta[D];
-    kde_draw_row<D>(a.x, a.cum_q, a.S, a.bw, id, a.prop_lo, a.prop_hi, theta);
-    if (a.theta) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) a.theta[(int64_t)j * a.stride + r] = theta[j];
-    }
-    if (!a.y && !a.dis && !a.log_prior && !a.accept) return;
-    const StepArgs<D, YD>& m = model_after_search(a);
-
-    // the prior's log-density: glabc_model_prior_log_prob; the distance and the acceptance need to know where it is -inf
-    float lp = 0.0f;
-    if (a.dis || a.log_prior || a.accept) {
-        lp = dist_log_prob<D>(m.prior, theta);
-        if (a.log_prior) a.log_prior[r] = lp;
-    }
-    if (!a.y && !a.dis && !a.accept) return;
-
-    // y: glabc_model_simulate(eps = NULL) under the noise key -- normal j is word pair (2j, 2j + 1) of the blocks (id, 0, b)
-    constexpr int NYB = (YD + 3) / 4;
-    float nrm[4 * NYB], eps[YD], y[YD];
-#pragma unroll
-    for (int b = 0; b < NYB; ++b) {
-        const glabc_u32x4 w = glabc_philox4x32_10(id_lo, id_hi, 0u, (uint32_t)b, a.noise_lo, a.noise_hi);
-        glabc_normal_pair(w.v[0], w.v[1], &nrm[4 * b], &nrm[4 * b + 1]);
-        glabc_normal_pair(w.v[2], w.v[3], &nrm[4 * b + 2], &nrm[4 * b + 3]);
-    }
-#pragma unroll
-    for (int j = 0; j < YD; ++j) eps[j] = nrm[j];
-    model_simulate<D, YD>(m, theta, eps, y);
-    if (a.y) {
-#pragma unroll
-        for (int j = 0; j < YD; ++j) a.y[(int64_t)j * a.stride + r] = y[j];
-    }
-    if (!a.dis && !a.accept) return;
-
-    // outside the prior's support the distance is +inf: a select, so y above is still the simulated row
-    const float d0 = model_discrepancy_rows<YD>(y, m.y_obs);
-    const float dis = lp == -__builtin_inff() ? __builtin_inff() : d0;
-    if (a.dis) a.dis[r] = dis;
-    if (!a.accept) return;
-
-    // the Model's own kernel relative to its mode, K(dis) / K(0), as in abc_draws_kernel
-    const glabc_u32x4 w = glabc_philox4x32_10(id_lo, id_hi, 0u, 0u, a.accept_lo, a.accept_hi);
-    const float u = glabc_uniform_f32(w.v[0]);
-    const float q = (dis - 0.0f) / m.kern_scale;
-    const float p = glabc_expf(-(0.5f * (q * q)));
-    a.accept[r] = u < p ? (uint8_t)1 : (uint8_t)0;              // a NaN distance: p is NaN, the comparison false; +inf: p is 0
-}
 
 template <int D, int YD>
 inline int launch_smc(const glabc_model* m, const glabc_kde* k, uint64_t seed, int64_t row0, const int64_t* ids, int64_t n,
                       int64_t stride, float* theta, float* y, float* dis, float* log_prior, uint8_t* accept, hipStream_t s)
 {
-    glabc_chains none;
-    std::memset(&none, 0, sizeof none);
-    SmcArgs<D, YD> a;
-    std::memset(&a, 0, sizeof a);
-    a.s = pack_args_rinv<D, YD>(m, nullptr, &m->prior, &none, nullptr, 0.0f);
-    a.x = k->x, a.cum_q = k->cum_q, a.S = k->n_samples;
-    for (int d = 0; d < D; ++d) a.bw[d] = k->bandwidth[d];
-    a.ids = ids;
-    a.row0 = row0, a.n = n, a.stride = stride;
-    const uint64_t kn = seed ^ GLABC_ABC_NOISE_KEY, ka = seed ^ GLABC_ABC_ACCEPT_KEY;
-    a.prop_lo = (uint32_t)seed, a.prop_hi = (uint32_t)(seed >> 32);
-    a.noise_lo = (uint32_t)kn, a.noise_hi = (uint32_t)(kn >> 32);
-    a.accept_lo = (uint32_t)ka, a.accept_hi = (uint32_t)(ka >> 32);
-    a.theta = theta, a.y = y, a.dis = dis, a.log_prior = log_prior, a.accept = accept;
+    SmcArgs<D, YD> a = pack_smc_args<D, YD>(m, k, seed, row0, ids, n, stride, theta, y, dis, log_prior, accept);
     for (a.first = 0; a.first < n; a.first += SMC_MAX_LAUNCH) {
         const int64_t part = n - a.first < SMC_MAX_LAUNCH ? n - a.first : SMC_MAX_LAUNCH;
         hipLaunchKernelGGL((smc_draws_kernel<D, YD>), dim3(grid_for(part, SMC_BLOCK)), dim3(SMC_BLOCK), 0, s, a);

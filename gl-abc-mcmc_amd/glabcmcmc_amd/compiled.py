@@ -48,6 +48,12 @@ a mixture program (``program(..., mixture=True)``: ``glabc_rtc_compile_mix`` up 
 Model above), launched by ``glabc_rtc_mix_steps``.  Its self-check runs it against ``glabc_propose_mix`` -> the compiled row callbacks
 -> ``glabc_select`` on the same Philox streams, with the caller's mixture.
 
+``rejection`` and ``smc`` run fused on a ``CompiledModel`` as well: ``draws_program()`` compiles the two draw kernels of
+``glabc_abc_draws`` / ``glabc_smc_draws`` around the source (``glabc_rtc_compile_draws``; a program of its own in the cache, no sampler
+kernel in it) and checks them, bit for bit, against the composition of entry points that specifies a draw (include/glabc.h) before
+it is handed out.  A user prior (``GLABC_USER_PRIOR``) and a Gamma prior have no draws program: theta is drawn from a DiagGaussian
+or Uniform descriptor prior there.
+
 Use + - * / fmaf sqrtf fabsf and the ``glabc_*`` functions of include/glabc_numerics.h (``glabc_expf``,
 ``glabc_logf``, ``glabc_sincos2pi`` ...) for results that a CPU build of the same source reproduces bit for bit.
 """
@@ -232,6 +238,174 @@ class CompiledModel:
                 "the run-time compiled mixture kernel (algorithm %d, batch size %d) disagrees with the split-phase path on %d of %d "
                 "chains after %d iterations: refusing to sample with it (use path='generic', and please report the "
                 "simulator source)" % (algo, batch_size, bad, n_chains, steps))
+        return True
+
+    # ---- the draws program: abc_draws_kernel and smc_draws_kernel around the source (rejection.py, smc.py) --------------------
+    DRAWS = "draws"
+
+    def draws_refusal(self):
+        """why this Model has no draws program (a sentence), or None"""
+        if self.user_prior:
+            return "the source announces GLABC_USER_PRIOR: the draw kernels draw theta from a descriptor prior"
+        try:
+            kind = self.prior.descriptor().kind
+        except (AttributeError, NotImplementedError, ValueError):
+            return "the prior %r has no descriptor()" % (self.prior,)
+        if kind not in (_capi.DIST_DIAG_GAUSS, _capi.DIST_UNIFORM):
+            return "the prior is neither DiagGaussian nor Uniform"
+        return None
+
+    def draws_program(self):
+        """The handle of the draws program (glabc_rtc_compile_draws), compiled once and self-checked (self_check_draws) before it is
+        handed out; a failed check raises SimulatorSelfCheckError, releases the program and is remembered."""
+        reason = self.draws_refusal()
+        if reason is not None:
+            raise ValueError("no draws program for this Model: " + reason)
+        key = (self.DRAWS,)
+        if key in self._failed:
+            raise SimulatorSelfCheckError(self._failed[key])
+        if key not in self._programs:
+            handle = C.c_void_p()
+            log = C.create_string_buffer(1 << 16)
+            rc = _capi.lib().glabc_rtc_compile_draws(self.simulator_source.encode(), self.theta_dim, self.y_dim, self.noise_dim,
+                                                     C.byref(handle), log, len(log))
+            if rc != _capi.OK:
+                raise SimulatorCompileError("glabc_rtc_compile_draws failed (status %d):\n%s" % (rc, log.value.decode(errors="replace")))
+            self._programs[key] = handle
+        if key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
+            try:
+                self.self_check_draws(self._programs[key])
+                self._checked.add(key)
+            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
+                handle = self._programs.pop(key, None)
+                if handle is not None:
+                    _capi.lib().glabc_rtc_release(handle)
+                if isinstance(exc, SimulatorSelfCheckError):
+                    self._failed[key] = str(exc)
+                raise
+        return self._programs[key]
+
+    def composed_draws(self, handle, desc, seed, row0, n, population=None):
+        """Draws row0 .. row0 + n - 1 as include/glabc.h specifies them, from the entry points a draw is composed of: theta from
+        glabc_dist_forward of the prior (glabc_kde_sample of `population`), eps from glabc_dist_forward of a standard DiagGaussian
+        under seed ^ GLABC_ABC_NOISE_KEY, y from glabc_rtc_simulate, the distance from glabc_rtc_model_rows / glabc_model_discrepancy,
+        log_prior from glabc_model_prior_log_prob (+inf rule applied) -> {name: device tensor}, theta (n, D) and y (n, YD)"""
+        lib, dev = _capi.lib(), engine.require_device(None)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        z = torch.empty(self.theta_dim, n, dtype=torch.float32, device=dev)
+        lq = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            if population is None:
+                _capi.check(lib.glabc_dist_forward(C.byref(desc.prior), n, seed, row0, z.data_ptr(), lq.data_ptr(), stream), "glabc_dist_forward")
+            else:
+                _capi.check(lib.glabc_kde_sample(C.byref(population.descriptor()), n, seed, row0, z.data_ptr(), stream), "glabc_kde_sample")
+            theta = z.t().contiguous()
+            e = torch.empty(self.noise_dim, n, dtype=torch.float32, device=dev)
+            _capi.check(lib.glabc_dist_forward(C.byref(desc.noise), n, seed ^ _capi.ABC_NOISE_KEY, row0, e.data_ptr(), lq.data_ptr(), stream),
+                        "glabc_dist_forward")
+            eps = e.t().contiguous()
+            y = torch.empty(n, self.y_dim, dtype=torch.float32, device=dev)
+            _capi.check(lib.glabc_rtc_simulate(handle, theta.data_ptr(), eps.data_ptr(), n, y.data_ptr(), stream), "glabc_rtc_simulate")
+            dis = torch.empty(n, dtype=torch.float32, device=dev)
+            if self.user_discrepancy:
+                _capi.check(lib.glabc_rtc_model_rows(handle, C.byref(desc), _capi.RTC_DISCREPANCY, y.data_ptr(), n, dis.data_ptr(), stream),
+                            "glabc_rtc_model_rows")
+            else:
+                _capi.check(lib.glabc_model_discrepancy(C.byref(desc), y.data_ptr(), n, dis.data_ptr(), stream), "glabc_model_discrepancy")
+            out = {"theta": theta, "y": y, "distance": dis}
+            if population is not None:
+                lp = torch.empty(n, dtype=torch.float32, device=dev)
+                _capi.check(lib.glabc_model_prior_log_prob(C.byref(desc), theta.data_ptr(), n, lp.data_ptr(), stream),
+                            "glabc_model_prior_log_prob")
+                out["log_prior"] = lp
+                out["distance"] = torch.where(lp == -float("inf"), torch.full_like(dis, float("inf")), dis)
+        return out
+
+    def composed_accept(self, desc, seed, ids, dis):
+        """The acceptance of include/glabc.h for the descriptor's kernel, from the library's own numerics on the device
+        (glabc_selftest_numerics: Philox, glabc_expf) and IEEE float32 arithmetic in NumPy: u < exp(-(0.5 (e e))), e = (dis - 0) / scale
+        -> uint8 host array.  `ids`, `dis`: host arrays."""
+        lib, dev = _capi.lib(), engine.require_device(None)
+        n = len(ids)
+        key = (seed ^ _capi.ABC_ACCEPT_KEY) & 0xFFFFFFFFFFFFFFFF
+        ctr = np.zeros((n, 6), np.uint32)
+        ids = np.asarray(ids, np.uint64)
+        ctr[:, 0], ctr[:, 1] = (ids & np.uint64(0xFFFFFFFF)).astype(np.uint32), (ids >> np.uint64(32)).astype(np.uint32)
+        ctr[:, 4], ctr[:, 5] = key & 0xFFFFFFFF, key >> 32
+        with np.errstate(all="ignore"):
+            e = (np.asarray(dis, np.float32) - np.float32(0.0)) / np.float32(desc.kern_scale)
+            arg = -(np.float32(0.5) * (e * e))
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            c = torch.from_numpy(ctr.view(np.int32)).to(dev)
+            w = torch.empty(n, 4, dtype=torch.int32, device=dev)
+            _capi.check(lib.glabc_selftest_numerics(6, c.data_ptr(), w.data_ptr(), n, stream), "glabc_selftest_numerics")
+            a = torch.from_numpy(np.ascontiguousarray(arg, np.float32)).to(dev)
+            p = torch.empty(n, dtype=torch.float32, device=dev)
+            _capi.check(lib.glabc_selftest_numerics(0, a.data_ptr(), p.data_ptr(), n, stream), "glabc_selftest_numerics")
+        w0 = w[:, 0].cpu().numpy().view(np.uint32)
+        u = (w0 >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        return (u < p.cpu().numpy()).astype(np.uint8)
+
+    def self_check_draws(self, handle, seed=20240229):
+        """The two draw kernels of a freshly compiled draws program against the composition that specifies a draw (composed_draws),
+        bit for bit: 320 draws in three runs of consecutive ids -- from 0, across 2^32 and above 2^40 --, listed out of order; theta,
+        y, distance (and log_prior) together, then each output alone; the SMC kernel from a population of 48 prior draws.  The
+        acceptance byte is compared with composed_accept where the kernel is the descriptor's; a user kernel (GLABC_USER_KERNEL) has
+        no entry point that evaluates it at a given distance, so its byte is only held to what must be: the same alone as with the
+        other outputs, and 0 where the distance is NaN or +inf.  Runs once per Model (a few ms); GLABC_RTC_SELF_CHECK=0 skips it."""
+        from .kernel_density import KernelDensity
+        lib, dev = _capi.lib(), engine.require_device(None)
+        desc = self.descriptor()
+        runs = [(0, 128), (2 ** 32 - 64, 128), (2 ** 40 + 5, 64)]
+        ids = np.concatenate([np.arange(a, a + k, dtype=np.int64) for a, k in runs])
+        order = np.random.default_rng(seed).permutation(ids.size)
+        ids_dev = torch.from_numpy(ids[order]).to(dev)
+        n = ids.size
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        # the population of the SMC kernel: 48 draws of the prior, Silverman's bandwidth
+        z = torch.empty(self.theta_dim, 48, dtype=torch.float32, device=dev)
+        lq = torch.empty(48, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _capi.check(lib.glabc_dist_forward(C.byref(desc.prior), 48, seed + 1, 0, z.data_ptr(), lq.data_ptr(), stream), "glabc_dist_forward")
+        population = KernelDensity("silverman", device=dev).fit(z.t().contiguous())
+
+        def fused(pop, want):
+            shapes = {"theta": (self.theta_dim, n), "y": (self.y_dim, n), "distance": (n,), "log_prior": (n,), "accept": (n,)}
+            out = {k: torch.empty(shapes[k], dtype=torch.uint8 if k == "accept" else torch.float32, device=dev) for k in want}
+            ptr = lambda k: out[k].data_ptr() if k in out else None          # noqa: E731
+            with torch.cuda.device(dev):
+                if pop is None:
+                    _capi.check(lib.glabc_rtc_abc_draws(handle, C.byref(desc), seed, 0, ids_dev.data_ptr(), n, n, ptr("theta"), ptr("y"),
+                                                        ptr("distance"), ptr("accept"), stream), "glabc_rtc_abc_draws")
+                else:
+                    _capi.check(lib.glabc_rtc_smc_draws(handle, C.byref(desc), C.byref(pop.descriptor()), seed, 0, ids_dev.data_ptr(), n, n,
+                                                        ptr("theta"), ptr("y"), ptr("distance"), ptr("log_prior"), ptr("accept"), stream),
+                                "glabc_rtc_smc_draws")
+            return {k: (v.t().contiguous() if k in ("theta", "y") else v).cpu().numpy() for k, v in out.items()}
+
+        def refuse(kernel, name, detail=""):
+            raise SimulatorSelfCheckError(
+                "the run-time compiled %s disagrees with the composition of entry points that specifies a draw in `%s`%s: refusing to "
+                "draw with it (use path='generic', and please report the simulator source)" % (kernel, name, detail))
+
+        for pop, kernel in ((None, "abc_draws_kernel"), (population, "smc_draws_kernel")):
+            names = ("theta", "y", "distance") + (("log_prior",) if pop is not None else ())
+            parts = [self.composed_draws(handle, desc, seed, a, k, pop) for a, k in runs]
+            want = {k: torch.cat([p[k] for p in parts]).cpu().numpy()[order] for k in names}
+            got = fused(pop, names + ("accept",))
+            for k in names:
+                if not np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)):
+                    refuse(kernel, k, " (%d of %d draws)" % (int((got[k].view(np.uint32) != want[k].view(np.uint32)).reshape(n, -1).any(axis=1).sum()), n))
+            if self.user_kernel:
+                if got["accept"][~np.isfinite(want["distance"])].any() or not np.isin(got["accept"], (0, 1)).all():
+                    refuse(kernel, "accept", " (a draw without a finite distance was accepted)")
+            elif not np.array_equal(got["accept"], self.composed_accept(desc, seed, ids[order], want["distance"])):
+                refuse(kernel, "accept")
+            for k in names + ("accept",):                               # each output alone: the scalar branches around the NULL ones
+                alone = fused(pop, (k,))[k]
+                if not np.array_equal(alone.view(np.uint8), got[k].view(np.uint8)):
+                    refuse(kernel, k, " asked for alone")
         return True
 
     def _gamma_prior(self):

@@ -12,8 +12,13 @@ ids in ascending order, and one ``glabc_abc_draws(ids=...)`` call that regenerat
 order statistic of the hard kernel is exact and sort-free: ``diagnostics.select`` over ``diagnostics.key_counts`` of the
 distances viewed as a (1, n_draws, 1) history.  There is no CPU implementation of this path.
 
-Generic path (``path="generic"``): plain torch for Models ``glabc_abc_draws`` refuses -- ``CompiledModel``, Gamma priors,
-callback Models.  theta comes from ``prior.forward`` in chunks, ``ABCset.generate_samples(theta, 1)`` and
+A ``CompiledModel`` runs the same path through ``glabc_rtc_abc_draws``: the kernel of ``glabc_abc_draws`` compiled around the user's
+simulator (``CompiledModel.draws_program``, compiled and checked once per Model), where the source has no prior of its own and the
+prior is a DiagGaussian or a Uniform.  ``path="auto"`` takes it where a GPU is present; a program that fails to compile or to check
+makes ``"auto"`` warn and run the generic path.  Which entry point a call runs is decided in one place, ``_path``.
+
+Generic path (``path="generic"``): plain torch for Models neither entry point takes -- a ``CompiledModel`` with a user prior, Gamma
+priors, callback Models.  theta comes from ``prior.forward`` in chunks, ``ABCset.generate_samples(theta, 1)`` and
 ``ABCset.discrepancy`` give the distance, the acceptance uniform is ``torch.rand``; ids are draw positions.  It runs wherever
 the Model's callbacks run, CPU tensors included.
 
@@ -24,6 +29,7 @@ NaN distance is never kept; a wanted rank that falls on a NaN is a ValueError.  
 """
 import ctypes as C
 import math
+import warnings
 from collections import namedtuple
 
 import numpy as np
@@ -90,19 +96,62 @@ def accepted(ABCset, epsilon=None):
     return desc if rc == _capi.OK else None
 
 
+class _Entry:
+    """The fused draws of one Model: its glabc_model and the entry points that take it -- glabc_abc_draws / glabc_smc_draws for the
+    built-in simulators, glabc_rtc_abc_draws / glabc_rtc_smc_draws with the draws program of a CompiledModel.  ``abc`` and ``smc`` take
+    the arguments of the C entry points after the Model (and the population), and raise on a status other than GLABC_OK."""
+
+    def __init__(self, desc, program=None):
+        self.desc, self.program = desc, program
+        self.theta_dim, self.y_dim = desc.theta_dim, desc.y_dim
+
+    def abc(self, *args):
+        lib = _capi.lib()
+        if self.program is None:
+            _capi.check(lib.glabc_abc_draws(C.byref(self.desc), *args), "glabc_abc_draws")
+        else:
+            _capi.check(lib.glabc_rtc_abc_draws(self.program, C.byref(self.desc), *args), "glabc_rtc_abc_draws")
+
+    def smc(self, kde_desc, *args):
+        lib = _capi.lib()
+        if self.program is None:
+            _capi.check(lib.glabc_smc_draws(C.byref(self.desc), C.byref(kde_desc), *args), "glabc_smc_draws")
+        else:
+            _capi.check(lib.glabc_rtc_smc_draws(self.program, C.byref(self.desc), C.byref(kde_desc), *args), "glabc_rtc_smc_draws")
+
+
 def _path(ABCset, path, epsilon):
+    """The one place that decides what a call runs -> the _Entry of the fused path, or None for the generic one.  "fused" raises where
+    no entry point takes the Model; "auto" goes generic there, and, for a CompiledModel, also without a GPU and (with a warning) where
+    the draws program fails to compile or to check."""
     if path not in ("auto", "fused", "generic"):
         raise ValueError('path is "auto", "fused" or "generic", got %r' % (path,))
-    desc = None if path == "generic" else accepted(ABCset, epsilon)
-    if path == "fused" and desc is None:
+    if path == "generic":
+        return None
+    desc = accepted(ABCset, epsilon)
+    if desc is not None:
+        return _Entry(desc)
+    from .compiled import CompiledModel, SimulatorCompileError, SimulatorSelfCheckError
+    reason = ABCset.draws_refusal() if isinstance(ABCset, CompiledModel) else None
+    if isinstance(ABCset, CompiledModel) and reason is None and (path == "fused" or torch.cuda.is_available()):
+        try:
+            return _Entry(ABCset.descriptor(epsilon), ABCset.draws_program())
+        except (SimulatorCompileError, SimulatorSelfCheckError) as exc:
+            if path == "fused":
+                raise
+            warnings.warn("the run-time compiled draw kernels are unavailable, running the generic path instead (%s)" % (exc,),
+                          RuntimeWarning, stacklevel=3)
+            return None
+    if path == "fused":
         raise ValueError('path="fused" needs a Model whose descriptor() glabc_abc_draws accepts (|theta| + noise or g-and-k with a '
-                         'DiagGaussian or Uniform prior), got %r' % (type(ABCset).__name__,))
-    return desc
+                         'DiagGaussian or Uniform prior) or a CompiledModel with a draws program, got %r%s'
+                         % (type(ABCset).__name__, "" if reason is None else " (%s)" % reason))
+    return None
 
 
 # ---------------------------------------------------------------------------------- the fused path
 def _launch(desc, seed, row0, ids, n, dev, want):
-    """glabc_abc_draws -> the dimension-major buffers {name: tensor} of the wanted outputs"""
+    """glabc_abc_draws (`desc`: the _Entry of the Model) -> the dimension-major buffers {name: tensor} of the wanted outputs"""
     out = {}
     if "theta" in want:
         out["theta"] = torch.empty(desc.theta_dim, n, dtype=torch.float32, device=dev)
@@ -115,15 +164,14 @@ def _launch(desc, seed, row0, ids, n, dev, want):
     ptr = lambda name: out[name].data_ptr() if name in out and n else None          # noqa: E731
     if n:
         with torch.cuda.device(dev):
-            _capi.check(_capi.lib().glabc_abc_draws(C.byref(desc), seed, row0, None if ids is None else ids.data_ptr(), n, n, ptr("theta"),
-                                                    ptr("y"), ptr("distance"), ptr("accept"),
-                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "glabc_abc_draws")
+            desc.abc(seed, row0, None if ids is None else ids.data_ptr(), n, n, ptr("theta"), ptr("y"), ptr("distance"), ptr("accept"),
+                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     return out
 
 
 def draws(ABCset, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, device=None):
-    """``glabc_abc_draws`` on device tensors -> Draws(theta (n, D), y (n, YD), distance (n,), accept (n,) uint8), None for what
-    `want` leaves out; theta and y are views of the kernel's dimension-major buffers.  Draw r has id ``ids[r]`` (any integers
+    """``glabc_abc_draws`` (a ``CompiledModel``: ``glabc_rtc_abc_draws``) on device tensors -> Draws(theta (n, D), y (n, YD),
+    distance (n,), accept (n,) uint8), None for what `want` leaves out; theta and y are views of the kernel's dimension-major buffers.  Draw r has id ``ids[r]`` (any integers
     in 0 .. 2^63 - 1, any order, repeats allowed; `n` must be their number) or ``row0 + r``; a draw depends on (Model, seed, id) only."""
     n = _count("n", n, 0)
     row0 = _count("row0", row0, 0)
@@ -132,9 +180,7 @@ def draws(ABCset, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, devi
         raise ValueError("want names one or more of %r, got %r" % (OUTPUTS, want))
     if seed is None or isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("seed must be an integer, got %r" % (seed,))
-    desc = accepted(ABCset, _epsilon(ABCset, epsilon, True))
-    if desc is None:
-        raise ValueError("glabc_abc_draws does not take this Model (%s): use sample(path=\"generic\")" % type(ABCset).__name__)
+    desc = _fused_entry(ABCset, _epsilon(ABCset, epsilon, True), "glabc_abc_draws")
     if ids is not None:
         if row0 != 0:
             raise ValueError("row0 must be 0 when ids are given, got %r" % (row0,))
@@ -150,17 +196,24 @@ def draws(ABCset, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, devi
     return Draws(out["theta"].t() if "theta" in out else None, out["y"].t() if "y" in out else None, out.get("distance"), out.get("accept"))
 
 
+def _fused_entry(ABCset, epsilon, what):
+    """the _Entry of draws(): _path's "fused", with the message of the entry point the caller names"""
+    try:
+        return _path(ABCset, "fused", epsilon)
+    except ValueError as exc:
+        raise ValueError("%s does not take this Model (%s): use sample(path=\"generic\") [%s]" % (what, type(ABCset).__name__, exc)) from None
+
+
 def _sweep(desc, seed, n_draws, dev, name):
     """one output of every draw 0 .. n_draws - 1, in launches of at most MAX_LAUNCH draws"""
     full = torch.empty(n_draws, dtype=torch.uint8 if name == "accept" else torch.float32, device=dev)
-    lib, size = _capi.lib(), full.element_size()
+    size = full.element_size()
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
         for row0 in range(0, n_draws, MAX_LAUNCH):
             k = min(MAX_LAUNCH, n_draws - row0)
             p = full.data_ptr() + size * row0
-            _capi.check(lib.glabc_abc_draws(C.byref(desc), seed, row0, None, k, k, None, None, p if name == "distance" else None,
-                                            p if name == "accept" else None, stream), "glabc_abc_draws")
+            desc.abc(seed, row0, None, k, k, None, None, p if name == "distance" else None, p if name == "accept" else None, stream)
     return full
 
 
@@ -270,7 +323,8 @@ def sample(ABCset, n_draws, *, kernel="model", epsilon=None, n_accept=None, quan
     n_draws), rows in ascending id.  kernel="model": the draws accepted with probability K_eps(distance) / K_eps(0) at
     ``ABCset.epsilon`` (or `epsilon`): independent exact draws from the samplers' target.  kernel="hard": the draws with
     distance <= epsilon, epsilon given or the order statistic that ``n_accept`` / ``quantile`` names (module docstring).
-    path: "auto" (fused where ``glabc_abc_draws`` takes the Model, else generic), "fused", "generic" (needs ``prior=``)."""
+    path: "auto" (fused where ``glabc_abc_draws`` takes the Model or a ``CompiledModel`` has a draws program and a GPU, else
+    generic), "fused", "generic" (needs ``prior=``)."""
     return _run(ABCset, n_draws, kernel, epsilon, n_accept, quantile, seed, device, path, prior)
 
 

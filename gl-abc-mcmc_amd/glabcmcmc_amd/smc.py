@@ -19,10 +19,11 @@ the soft generation), sized from the acceptance rate seen so far; ``torch.nonzer
 are kept, and the FIRST N BY ID are the generation: the result depends on (Model, N, settings, seed), never on how the sweep was
 cut.  One ``glabc_smc_draws(ids=...)`` call regenerates theta, y, distance and log-prior of the kept draws.  A proposal of prior
 density 0 has the distance +inf and is never kept.  Generation t runs under the key (seed + t * 0x632BE59BD9B4E019) mod 2^64.
-There is no CPU implementation of this path.
+There is no CPU implementation of this path.  A ``CompiledModel`` runs it through ``glabc_rtc_smc_draws``, the same kernel compiled
+around the user's simulator (``rejection._path`` decides, as for ``rejection.sample``).
 
-Generic path (``path="generic"``): plain torch on the Model's callbacks and on ``prior`` (``forward`` and ``log_prob``), for
-``CompiledModel``, Gamma priors and callback Models, CPU tensors included.  Ancestors come from ``torch.multinomial``, the
+Generic path (``path="generic"``): plain torch on the Model's callbacks and on ``prior`` (``forward`` and ``log_prob``), for a
+``CompiledModel`` with a user prior, Gamma priors and callback Models, CPU tensors included.  Ancestors come from ``torch.multinomial``, the
 perturbation from ``torch.randn`` (torch's global generator), the mixture density is a chunked float64 ``logsumexp``; ids are
 draw positions.  Ladder, selection and weights are the code the fused path runs.
 
@@ -35,7 +36,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _capi, engine, rejection
+from . import engine, rejection
 from .kernel_density import KernelDensity
 
 SEED_STEP = 0x632BE59BD9B4E019    # generation t draws under the key (seed + t * SEED_STEP) mod 2^64
@@ -50,22 +51,20 @@ Draws = namedtuple("Draws", "theta y distance log_prior accept")
 
 # ---------------------------------------------------------------------------------- glabc_smc_draws
 def _launch(desc, kde, seed, row0, ids, n, dev, want):
-    """glabc_smc_draws -> the dimension-major buffers {name: tensor} of the wanted outputs"""
+    """glabc_smc_draws (`desc`: the rejection._Entry of the Model) -> the dimension-major buffers {name: tensor} of the wanted outputs"""
     shapes = {"theta": (desc.theta_dim, n), "y": (desc.y_dim, n), "distance": (n,), "log_prior": (n,), "accept": (n,)}
     out = {name: torch.empty(shapes[name], dtype=torch.uint8 if name == "accept" else torch.float32, device=dev) for name in want}
     ptr = lambda name: out[name].data_ptr() if name in out and n else None          # noqa: E731
     if n:
         with torch.cuda.device(dev):
-            _capi.check(_capi.lib().glabc_smc_draws(C.byref(desc), C.byref(kde.descriptor()), seed, row0,
-                                                    None if ids is None else ids.data_ptr(), n, n, ptr("theta"), ptr("y"), ptr("distance"),
-                                                    ptr("log_prior"), ptr("accept"),
-                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "glabc_smc_draws")
+            desc.smc(kde.descriptor(), seed, row0, None if ids is None else ids.data_ptr(), n, n, ptr("theta"), ptr("y"), ptr("distance"),
+                     ptr("log_prior"), ptr("accept"), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     return out
 
 
 def draws(ABCset, population, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, device=None):
-    """``glabc_smc_draws`` on device tensors -> Draws(theta (n, D), y (n, YD), distance (n,), log_prior (n,), accept (n,) uint8),
-    None for what `want` leaves out; theta and y are views of the kernel's dimension-major buffers.  `population` is a fitted
+    """``glabc_smc_draws`` (a ``CompiledModel``: ``glabc_rtc_smc_draws``) on device tensors -> Draws(theta (n, D), y (n, YD),
+    distance (n,), log_prior (n,), accept (n,) uint8), None for what `want` leaves out; theta and y are views of the kernel's dimension-major buffers.  `population` is a fitted
     ``KernelDensity`` of theta_dim features.  Draw r has id ``ids[r]`` (any integers in 0 .. 2^63 - 1, any order, repeats allowed;
     `n` must be their number) or ``row0 + r``; a draw depends on (Model, population, seed, id) only.  The distance of a proposal
     of prior density 0 is +inf."""
@@ -76,9 +75,7 @@ def draws(ABCset, population, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilo
         raise ValueError("want names one or more of %r, got %r" % (OUTPUTS, want))
     if seed is None or isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("seed must be an integer, got %r" % (seed,))
-    desc = rejection.accepted(ABCset, rejection._epsilon(ABCset, epsilon, True))
-    if desc is None:
-        raise ValueError("glabc_smc_draws does not take this Model (%s): use sample(path=\"generic\")" % type(ABCset).__name__)
+    desc = rejection._fused_entry(ABCset, rejection._epsilon(ABCset, epsilon, True), "glabc_smc_draws")
     if not isinstance(population, KernelDensity) or not population._fitted:
         raise ValueError("population must be a fitted KernelDensity, got %r" % (population,))
     if population.dim != desc.theta_dim:

@@ -890,6 +890,54 @@ int glabc_smc_draws(const glabc_model* model, const glabc_kde* population, uint6
                     int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out, float* log_prior_out,
                     uint8_t* accept_out, void* stream);
 
+/* ---- The two draw kernels around a USER simulator (csrc/glabc_rtc.hip): glabc_abc_draws and glabc_smc_draws for GLABC_SIM_USER Models.
+ * glabc_rtc_compile_draws compiles (hiprtc, gfx950) the templates those two entry points are instantiated from -- abc_draws_kernel
+ * (csrc/glabc_abc.h) and smc_draws_kernel (csrc/glabc_smc.h) -- around `simulator_source` (the source of glabc_rtc_compile, with its
+ * optional GLABC_USER_DISCREPANCY / GLABC_USER_KERNEL), plus the two row kernels every program holds: glabc_rtc_simulate,
+ * glabc_rtc_hooks, glabc_rtc_model_rows and glabc_rtc_release take a draws program as any other.  It holds no sampler kernel:
+ * glabc_rtc_steps and glabc_rtc_mix_steps refuse it with GLABC_ERR_KIND (a third kind of program beside the sampler and the mixture
+ * programs).  Compile options, the log and GLABC_ERR_ARG / GLABC_ERR_NO_DEVICE are glabc_rtc_compile's; a kernel that spills
+ * registers is named in the log and handed out.  Refusals of glabc_rtc_compile_draws, in this order:
+ *   a NULL source or out                                                                          GLABC_ERR_NULL
+ *   theta_dim, y_dim or noise_dim outside 1 .. GLABC_MAX_DIM                                      GLABC_ERR_DIM
+ *   a source that announces GLABC_USER_PRIOR (a line in the log says so): theta is drawn from the descriptor's prior, and
+ *     generation 0 of ABC-SMC takes that for the prior                                            GLABC_ERR_KIND
+ *
+ * Ids, layouts, NULL outputs, the 2^30-draw launches and the 64-bit indices of glabc_rtc_abc_draws / glabc_rtc_smc_draws are
+ * glabc_abc_draws' / glabc_smc_draws'.  Specification of draw `id`, a composition of entry points of this header (nd = noise_dim):
+ *     theta     = row id of glabc_dist_forward(&model->prior, ., seed, .)                 (glabc_rtc_abc_draws)
+ *                 row id of glabc_kde_sample(population, ., seed, .)                      (glabc_rtc_smc_draws)
+ *     eps       = row id of glabc_dist_forward(a DiagGaussian of dimension nd, location 0 and scale 1, ., seed ^ GLABC_ABC_NOISE_KEY, .):
+ *                 the Philox blocks (key; id_lo, id_hi, 0, b), b < ceil(nd / 4), Box-Muller pairs of words (2i, 2i + 1) -- the blocks
+ *                 and pairs of the built-in kernels' noise; 0 + 1 * e is e
+ *     y         = glabc_rtc_simulate(program, theta, eps)
+ *     dis       = glabc_rtc_model_rows(program, model, GLABC_RTC_DISCREPANCY, y) where the source announces GLABC_USER_DISCREPANCY,
+ *                 else glabc_model_discrepancy(model, y); glabc_rtc_smc_draws: +inf where log_prior == -inf, as in glabc_smc_draws
+ *     log_prior = glabc_model_prior_log_prob(model, theta)                                 (glabc_rtc_smc_draws)
+ *     u         = glabc_uniform_f32(word 0 of Philox(seed ^ GLABC_ABC_ACCEPT_KEY; id_lo, id_hi, 0, 0))
+ *     p         = without GLABC_USER_KERNEL: e = (dis - 0.0f) / kern_scale, p = glabc_expf(-(0.5f * (e * e))), as in glabc_abc_draws;
+ *                 with it: p = glabc_expf(lk(dis) - lk(0.0f)), lk(d) = glabc_user_log_kernel(d, kern_scale) -- the ratio
+ *                 K(dis) / K(0) from its two logarithms
+ *     accept    = u < p ? 1 : 0                    (a NaN p: 0)
+ * Refusals of the two, in this order; a refused call launches nothing and writes nothing:
+ *   a NULL program or model, or every output NULL                                                 GLABC_ERR_NULL
+ *   model->sim_kind != GLABC_SIM_USER                                                             GLABC_ERR_KIND
+ *   a program that glabc_rtc_compile_draws did not make                                           GLABC_ERR_KIND
+ *   model->theta_dim, y_dim or noise.dim differ from the program's                                GLABC_ERR_DIM
+ *   a prior that is not DiagGaussian / Uniform, or whose dim != theta_dim                         GLABC_ERR_KIND
+ *   glabc_rtc_smc_draws: the population as glabc_smc_draws refuses it (a NULL population: GLABC_ERR_NULL; dim, n_samples, x / log_w,
+ *     bandwidth; a NULL cum_q: GLABC_ERR_NULL; population->dim != theta_dim: GLABC_ERR_DIM)
+ *   n < 0, stride < n, row0 < 0, or row0 != 0 together with ids                                    GLABC_ERR_ARG
+ * n == 0 returns GLABC_OK and writes nothing.  glabc_abc_draws and glabc_smc_draws keep refusing GLABC_SIM_USER.  GLABC_VERSION and
+ * GLABC_STREAM_LAYOUT are unchanged. */
+int glabc_rtc_compile_draws(const char* simulator_source, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
+                            glabc_rtc_program** out, char* log, int64_t log_size);
+int glabc_rtc_abc_draws(const glabc_rtc_program* program, const glabc_model* model, uint64_t seed, int64_t row0, const int64_t* ids,
+                        int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out, uint8_t* accept_out, void* stream);
+int glabc_rtc_smc_draws(const glabc_rtc_program* program, const glabc_model* model, const glabc_kde* population, uint64_t seed,
+                        int64_t row0, const int64_t* ids, int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out,
+                        float* log_prior_out, uint8_t* accept_out, void* stream);
+
 /* AGLMCMC.py:199-204 (and :104-109): weights of a proposal pool from its stored discrepancies,
  * w[r] = exp((prior(theta_r) + calculate_log_kernel_dis(dis_r)) - log_q[r]), NaN -> 0.  The threshold is the one in
  * model->kern_* (the caller passes a copy of its descriptor with the annealed eps_hat, Mixture.py:47-53).
