@@ -286,6 +286,32 @@ inline int check_histogram(const float* history, int64_t n_rows, int32_t theta_d
     return GLABC_OK;
 }
 
+// ---- glabc_histogram2d / glabc_cross_moments: the same history, in the order include/glabc.h lists the refusals.  lo and hi are
+// looked at for the coordinates a pair uses only
+inline int check_histogram2d(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_pairs,
+                             const int32_t* pairs, int32_t n_bins, const double* lo, const double* hi, const uint64_t* counts)
+{
+    if (!pairs) return GLABC_ERR_NULL;
+    if (int e = check_counts_history(history, n_rows, theta_dim, n_chains, stride, lo, hi, counts)) return e;
+    if (n_pairs < 1 || n_pairs > GLABC_MAX_PAIRS) return GLABC_ERR_ARG;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int32_t a = pairs[2 * p], b = pairs[2 * p + 1];
+        if (a < 0 || a >= theta_dim || b < 0 || b >= theta_dim || a == b) return GLABC_ERR_ARG;
+    }
+    if (n_bins < 1 || n_bins > GLABC_MAX_JOINT_BINS) return GLABC_ERR_ARG;
+    for (int q = 0; q < 2 * n_pairs; ++q) {
+        const int32_t j = pairs[q];
+        if (!std::isfinite(lo[j]) || !std::isfinite(hi[j]) || !(lo[j] < hi[j])) return GLABC_ERR_ARG;
+    }
+    return GLABC_OK;
+}
+
+inline int check_cross_moments(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride,
+                               const double* mean_out, const double* cov_out)
+{
+    return check_autocov(history, n_rows, theta_dim, n_chains, stride, 0, mean_out, cov_out);
+}
+
 // ---- glabc_abc_draws: the Model a fused rejection draw is compiled for and the range of draws, in the order include/glabc.h lists
 // the refusals.  The parameters' values are not looked at: a draw from a prior of scale 0 or NaN is what the arithmetic says it is
 inline int check_abc_model(const glabc_model* m)

@@ -39,8 +39,18 @@ The counts are integers: the same bits in every launch geometry, and additive ov
 quantiles of the whole job.  ``histogram`` is one ``glabc_histogram`` launch, its default range the exact minimum and maximum.
 No slab of chains is ever cut for these: the kernels index with 64-bit scalars and size their own grid.
 
+The joint posterior.  ``histogram2d`` counts pairs of coordinates into bins x bins grids (``glabc_histogram2d``,
+csrc/glabc_joint.hip: the marginal histogram's bin arithmetic on both axes, integer counts, additive over shards of chains under
+an explicit range); ``hpd_levels`` / ``hpd_mask`` read the highest-density levels and regions off a grid on the host -- what a
+filled contour plot of (theta_i, theta_j) draws.  ``cross_moments`` gives every chain's means and covariance of all pairs of
+coordinates in float64 in a specified order (``glabc_cross_moments``); ``joint_terms`` reduces a shard of chains to additive
+sums, ``combine_joint`` adds shards, and ``covariance`` / ``correlation`` are those of all M n pooled draws:
+
+    cov = (n sum_c cov_c + n sum_c (m_c - m)(m_c - m)^T) / (M n - 1),      m the grand mean
+
 Out of scope: rank-normalised bulk / tail ESS (selection gives a few ranks, not all of them), per-chain ESS (``autocovariance``
-returns the per-chain numbers), joint histograms, weighted draws, and accumulating lagged products inside the sampler kernels.
+returns the per-chain numbers), multivariate ESS, weighted draws, grids in more than two dimensions or with unequal bin counts
+per axis, kernel smoothing of a grid, and accumulating lagged products or any of the above inside the sampler kernels.
 """
 import ctypes as C
 from collections import namedtuple
@@ -63,6 +73,11 @@ MAX_PREFIXES = 8                  # GLABC_MAX_PREFIXES: prefixes per coordinate 
 MAX_BINS = 4096                   # GLABC_MAX_BINS
 UNUSED_PREFIX = 0xFFFFFFFF        # a slot of a prefix table that counts nothing; also the key of every NaN
 Histogram = namedtuple("Histogram", "counts edges below above nan")
+MAX_PAIRS = 28                    # GLABC_MAX_PAIRS: pairs of one glabc_histogram2d launch
+MAX_JOINT_BINS = 128              # GLABC_MAX_JOINT_BINS, per axis
+JointHistogram = namedtuple("JointHistogram", "counts pairs edges outside nan")
+# additive over shards of chains (M adds up, n must agree)
+JointTerms = namedtuple("JointTerms", "M n sum_mean sum_mean_outer sum_cov")
 
 
 # ---------------------------------------------------------------------------------- arguments
@@ -452,6 +467,32 @@ def interval(history, prob=0.95, layout="rows"):
     return lower, upper
 
 
+def _check_range(range, d):
+    """-> float64 [D][2] of an explicit range, (lo, hi) or [D][2]"""
+    try:
+        lim = np.array(np.broadcast_to(np.asarray(range, np.float64), (d, 2)))
+    except (TypeError, ValueError):
+        raise ValueError("range is (lo, hi) or [D = %d][2], got %r" % (d, range)) from None
+    if not (np.isfinite(lim).all() and (lim[:, 0] < lim[:, 1]).all()):
+        raise ValueError("range needs finite lo < hi, got %r" % (range,))
+    return lim
+
+
+def _exact_range(h):
+    """-> float64 [D][2]: each coordinate's exact minimum and maximum (NaNs aside) of the chain-major rows `h`, by the selection;
+    a constant coordinate widened by +-0.5"""
+    def first_and_last(total, n_nan):
+        if (total == n_nan).any():
+            raise ValueError("a coordinate holds nothing but NaN: no range to bin")
+        return np.stack([np.zeros_like(total), total - n_nan - 1])
+    ends, _, _ = _walk(_counter(h, "chain_major"), first_and_last)
+    lim = np.ascontiguousarray(ends.astype(np.float64).T)
+    if not np.isfinite(lim).all():
+        raise ValueError("the draws' range %r is not finite: pass range=" % (lim.tolist(),))
+    lim[lim[:, 0] == lim[:, 1]] += (-0.5, 0.5)
+    return lim
+
+
 def histogram(history, bins=64, range=None, layout="rows"):
     """-> Histogram(counts uint64 [D][bins], edges float64 [D][bins + 1], below, above, nan uint64 [D]): `bins` equal bins per
     coordinate over `range` = (lo, hi) or [D][2], the last one closed as NumPy's; values under lo, over hi and NaNs are counted
@@ -460,24 +501,10 @@ def histogram(history, bins=64, range=None, layout="rows"):
     if isinstance(bins, bool) or bins != int(bins) or not 1 <= bins <= MAX_BINS:
         raise ValueError("bins must be an integer in 1..%d, got %r" % (MAX_BINS, bins))
     bins = int(bins)
-    if range is not None:
-        try:
-            lim = np.array(np.broadcast_to(np.asarray(range, np.float64), (d, 2)))
-        except (TypeError, ValueError):
-            raise ValueError("range is (lo, hi) or [D = %d][2], got %r" % (d, range)) from None
-        if not (np.isfinite(lim).all() and (lim[:, 0] < lim[:, 1]).all()):
-            raise ValueError("range needs finite lo < hi, got %r" % (range,))
+    lim = None if range is None else _check_range(range, d)
     h = _chain_major(history, layout)
-    if range is None:
-        def first_and_last(total, n_nan):
-            if (total == n_nan).any():
-                raise ValueError("a coordinate holds nothing but NaN: no range to bin")
-            return np.stack([np.zeros_like(total), total - n_nan - 1])
-        ends, _, _ = _walk(_counter(h, "chain_major"), first_and_last)
-        lim = np.ascontiguousarray(ends.astype(np.float64).T)
-        if not np.isfinite(lim).all():
-            raise ValueError("the draws' range %r is not finite: pass range=" % (lim.tolist(),))
-        lim[lim[:, 0] == lim[:, 1]] += (-0.5, 0.5)
+    if lim is None:
+        lim = _exact_range(h)
     lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
     n_rows, _, stride = h.shape
     counts = torch.zeros(d, bins + 3, dtype=torch.int64, device=h.device)
@@ -488,3 +515,196 @@ def histogram(history, bins=64, range=None, layout="rows"):
     counts = counts.cpu().numpy().view(np.uint64)
     edges = np.stack([np.linspace(lo[j], hi[j], bins + 1) for j in np.arange(d)])
     return Histogram(counts[:, :bins].copy(), edges, counts[:, bins].copy(), counts[:, bins + 1].copy(), counts[:, bins + 2].copy())
+
+
+# ---------------------------------------------------------------------------------- the joint posterior: the device part
+def _check_pairs(pairs, d):
+    """-> int32 [P][2]; None: every i < j"""
+    if d < 2:
+        raise ValueError("a joint histogram needs two coordinates, the history has %d" % d)
+    if pairs is None:
+        return np.array([(i, j) for i in np.arange(d) for j in np.arange(i + 1, d)], np.int32)
+    table = np.asarray(pairs)
+    if table.ndim != 2 or table.shape[1] != 2 or table.shape[0] < 1 or table.dtype.kind not in "ui":
+        raise ValueError("pairs are integers [P >= 1][2], got shape %r of %s" % (table.shape, table.dtype))
+    table = table.astype(np.int64)
+    if ((table < 0) | (table >= d)).any() or (table[:, 0] == table[:, 1]).any():
+        raise ValueError("a pair is two different coordinates in 0..%d, got %r" % (d - 1, table.tolist()))
+    return np.ascontiguousarray(table.astype(np.int32))
+
+
+def histogram2d(history, pairs=None, bins=64, range=None, layout="rows"):
+    """-> JointHistogram(counts uint64 [P][bins][bins], pairs int [P][2], edges float64 [D][bins + 1], outside, nan uint64 [P]):
+    for every pair (a, b) of coordinates (None: all i < j) the `bins` x `bins` grid of the draws (row t, chain c), axis 0 along
+    coordinate a and axis 1 along b as in numpy.histogram2d(x_a, x_b), each axis binned as ``histogram`` bins it.  A draw with a NaN in either coordinate is counted in `nan`; otherwise one
+    with a value under lo or over hi in either coordinate in `outside`.  (a, b) and (b, a) are each other's transposes and a pair
+    may repeat; more than 28 pairs go in several ``glabc_histogram2d`` launches.  range = (lo, hi) or [D][2]; range=None: each
+    coordinate's exact minimum and maximum (NaNs aside), a constant coordinate widened by +-0.5, as ``histogram``.  With an
+    explicit `range` the counts are additive over shards of chains (and slices of rows): a sharded job all-reduces them.
+    ``hpd_levels`` turns a grid into the levels a contour plot draws."""
+    _, _, d, _ = _check(history, layout, 0)
+    table = _check_pairs(pairs, d)
+    if isinstance(bins, bool) or bins != int(bins) or not 1 <= bins <= MAX_JOINT_BINS:
+        raise ValueError("bins must be an integer in 1..%d, got %r" % (MAX_JOINT_BINS, bins))
+    bins = int(bins)
+    lim = None if range is None else _check_range(range, d)
+    h = _chain_major(history, layout)
+    if lim is None:
+        lim = _exact_range(h)
+    lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+    n_rows, _, stride = h.shape
+    cells = bins * bins
+    out = np.zeros((table.shape[0], cells + 2), np.uint64)
+    stream = torch.cuda.current_stream(h.device).cuda_stream
+    with torch.cuda.device(h.device):
+        for p0 in np.arange(0, table.shape[0], MAX_PAIRS):
+            part = np.ascontiguousarray(table[p0:p0 + MAX_PAIRS])
+            k = part.shape[0]
+            counts = torch.zeros(k, cells + 2, dtype=torch.int64, device=h.device)
+            _capi.check(_capi.lib().glabc_histogram2d(h.data_ptr(), n_rows, d, stride, stride, k, part.ctypes.data, bins, lo.ctypes.data,
+                                                      hi.ctypes.data, counts.data_ptr(), C.c_void_p(stream)), "glabc_histogram2d")
+            out[p0:p0 + k] = counts.cpu().numpy().view(np.uint64)
+    edges = np.stack([np.linspace(lo[j], hi[j], bins + 1) for j in np.arange(d)])
+    return JointHistogram(out[:, :cells].reshape(-1, bins, bins).copy(), table.astype(np.int64), edges, out[:, cells].copy(),
+                          out[:, cells + 1].copy())
+
+
+def _cross(h, chain0, n_chains, mean, cov):
+    """glabc_cross_moments on chains [chain0, chain0 + n_chains) of the chain-major rows `h`"""
+    n_rows, d, stride = h.shape
+    stream = torch.cuda.current_stream(h.device).cuda_stream
+    with torch.cuda.device(h.device):
+        _capi.check(_capi.lib().glabc_cross_moments(h.data_ptr() + 4 * chain0, n_rows, d, n_chains, stride, mean.data_ptr(),
+                                                    cov.data_ptr(), C.c_void_p(stream)), "glabc_cross_moments")
+
+
+def cross_moments(history, layout="rows"):
+    """-> (mean [D][C], cov [D (D + 1) / 2][C]): float64 device tensors straight from the kernel, per chain; cov is the biased
+    (1/n) covariance of coordinates i <= j at row i * D - i (i - 1) / 2 + (j - i), its diagonal ``autocovariance``'s lag 0"""
+    _, c, d, _ = _check(history, layout, 0)
+    h = _chain_major(history, layout)
+    mean = torch.empty(d, c, dtype=torch.float64, device=h.device)
+    cov = torch.empty(d * (d + 1) // 2, c, dtype=torch.float64, device=h.device)
+    _cross(h, 0, c, mean, cov)
+    return mean, cov
+
+
+def joint_terms(history, layout="rows"):
+    """The additive sufficient statistics of the covariance of a shard of chains (float64 host arrays, see JointTerms): M, n and
+    the sums over chains of mean [D], of mean mean^T [D][D] and of the per-chain biased covariance [D][D].  The chains go through
+    the kernel in slabs, as in ``terms``"""
+    n, c, d, _ = _check(history, layout, 0)
+    h = _chain_major(history, layout)
+    tri = d * (d + 1) // 2
+    per_chain = 8 * (d + tri + d * d)                 # mean, cov and the outer products of the means, float64
+    slab = min(_SLAB_BYTES, h.numel()) // per_chain // 64 * 64
+    slab = min(c, max(slab, 64))
+    mean = torch.empty(d, slab, dtype=torch.float64, device=h.device)
+    cov = torch.empty(tri, slab, dtype=torch.float64, device=h.device)
+    s_mean = torch.zeros(d, dtype=torch.float64, device=h.device)
+    s_outer = torch.zeros(d, d, dtype=torch.float64, device=h.device)
+    s_cov = torch.zeros(tri, dtype=torch.float64, device=h.device)
+    for chain0 in np.arange(0, c, slab):
+        k = min(slab, c - int(chain0))
+        m, v = (mean, cov) if k == slab else (mean.view(-1)[:d * k].view(d, k), cov.view(-1)[:tri * k].view(tri, k))
+        _cross(h, int(chain0), k, m, v)
+        s_mean += m.sum(dim=1)
+        s_outer += (m[:, None, :] * m[None, :, :]).sum(dim=2)
+        s_cov += v.sum(dim=1)
+    packed = s_cov.cpu().numpy()
+    i, j = np.triu_indices(d)                          # row-major upper triangle: the packed order
+    full = np.empty((d, d))
+    full[i, j] = packed
+    full[j, i] = packed
+    return JointTerms(c, n, s_mean.cpu().numpy(), s_outer.cpu().numpy(), full)
+
+
+# ---------------------------------------------------------------------------------- the joint posterior: shards and formulas
+def combine_joint(list_of_terms):
+    """JointTerms of the concatenated shards of chains: a plain sum (n must agree)"""
+    parts = list(list_of_terms)
+    if not parts:
+        raise ValueError("combine_joint needs at least one JointTerms")
+    first = parts[0]
+    for t in parts[1:]:
+        if t.n != first.n or np.shape(t.sum_cov) != np.shape(first.sum_cov):
+            raise ValueError("shards differ in rows or coordinates: (%d, %r) and (%d, %r)"
+                             % (first.n, np.shape(first.sum_cov), t.n, np.shape(t.sum_cov)))
+    add = lambda field: sum(np.asarray(getattr(t, field), np.float64) for t in parts)          # noqa: E731
+    return JointTerms(sum(int(t.M) for t in parts), first.n, add("sum_mean"), add("sum_mean_outer"), add("sum_cov"))
+
+
+def covariance(x, layout="rows"):
+    """-> float64 [D][D]: the covariance of all M n pooled draws of a history (or of its JointTerms) about the grand mean, with
+    divisor M n - 1 -- what numpy.cov of the pooled draws estimates:
+        (n sum_c cov_c + n sum_c (m_c - m)(m_c - m)^T) / (M n - 1),      sum_c (m_c - m)(m_c - m)^T = sum_mean_outer - sum_mean sum_mean^T / M
+    symmetric by construction"""
+    draws = x.M * x.n if isinstance(x, JointTerms) else np.prod(_check(x, layout, 0)[:2])
+    if draws < 2:
+        raise ValueError("a covariance needs two draws, got M n = %d" % draws)
+    t = x if isinstance(x, JointTerms) else joint_terms(x, layout)
+    m, n = float(t.M), float(t.n)
+    s = np.asarray(t.sum_mean, np.float64)
+    between = np.asarray(t.sum_mean_outer, np.float64) - np.outer(s, s) / m
+    between = 0.5 * (between + between.T)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (n * np.asarray(t.sum_cov, np.float64) + n * between) / (m * n - 1.0)
+
+
+def correlation(x, layout="rows"):
+    """-> float64 [D][D]: ``covariance`` divided by the square roots of its diagonal; NaN where a variance is 0, no exception"""
+    v = covariance(x, layout)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sd = np.sqrt(np.diag(v))
+        r = v / np.outer(sd, sd)
+    r[(sd == 0.0)[:, None] | (sd == 0.0)[None, :]] = np.nan
+    return r
+
+
+# ---------------------------------------------------------------------------------- highest-density levels of a grid (host)
+def _check_grids(counts):
+    c = np.asarray(counts)
+    if c.ndim < 2 or c.dtype.kind not in "ui" or (c.dtype.kind == "i" and (c < 0).any()):
+        raise ValueError("counts are non-negative integers [..][bins][bins], got shape %r of %s" % (c.shape, c.dtype))
+    c = c.astype(np.uint64)
+    flat = c.reshape(-1, c.shape[-2] * c.shape[-1])
+    if flat.shape[1] == 0 or not flat.any(axis=1).all():
+        raise ValueError("an empty grid has no highest-density region")
+    return c, flat
+
+
+def hpd_levels(counts, probs=(0.5, 0.9, 0.95)):
+    """Highest-posterior-density levels of a pair's grid [bins][bins] (or of a stack of grids [..][bins][bins]), on the host in
+    integer arithmetic.  With N_in the sum of the grid and need = ceil(p N_in) (the product one float64 multiplication, so that
+    0.8 of 20 draws is 16 of them; at most N_in), the level of probability p is the largest count value v with the sum of the
+    counts g >= v at least need: the region {g >= v} is the smallest set of whole level sets that holds
+    the fraction p of the binned draws.  -> (level uint64 [..][Q], mass uint64 [..][Q] = the sum over the region, n_bins_inside
+    int64 [..][Q]).  level / (N bin area), bin area the product of the two axes' bin widths, is the density threshold a filled
+    contour plot of the grid draws at p; equal bins make the region the same for counts and densities.  An empty grid raises"""
+    import math
+    q = np.atleast_1d(np.asarray(probs, np.float64))
+    if q.ndim != 1 or q.size < 1 or not ((q > 0.0) & (q <= 1.0)).all():
+        raise ValueError("probs are numbers in (0, 1], got %r" % (probs,))
+    c, flat = _check_grids(counts)
+    level = np.empty((flat.shape[0], q.size), np.uint64)
+    mass = np.empty((flat.shape[0], q.size), np.uint64)
+    inside = np.empty((flat.shape[0], q.size), np.int64)
+    for g, grid in enumerate(flat):
+        s = np.sort(grid)[::-1]
+        cum = np.cumsum(s, dtype=np.uint64)
+        total = int(cum[-1])
+        for i, p in enumerate(q):
+            need = min(int(math.ceil(float(p) * float(total))), total)
+            v = s[int(np.searchsorted(cum, np.uint64(need), side="left"))]
+            region = grid >= v
+            level[g, i], mass[g, i], inside[g, i] = v, grid[region].sum(dtype=np.uint64), int(region.sum())
+    lead = c.shape[:-2]
+    return level.reshape(lead + (q.size,)), mass.reshape(lead + (q.size,)), inside.reshape(lead + (q.size,))
+
+
+def hpd_mask(counts, prob):
+    """-> bool, the shape of `counts`: counts >= the ``hpd_levels`` level of `prob`, the highest-density region of each grid"""
+    if np.ndim(prob) != 0:
+        raise ValueError("prob is one number in (0, 1], got %r" % (prob,))
+    level = hpd_levels(counts, (prob,))[0]
+    return np.asarray(counts).astype(np.uint64) >= level[..., 0][..., None, None]

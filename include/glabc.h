@@ -773,6 +773,48 @@ int glabc_key_counts(const float* history, int64_t n_rows, int32_t theta_dim, in
 int glabc_histogram(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_bins,
                     const double* lo, const double* hi, uint64_t* counts, void* stream);
 
+/* ---- the joint posterior of a history: pair histograms (integer counts, additive over shards of chains and slices of rows) and
+ * per-chain cross moments, the sufficient statistics of the posterior covariance (glabcmcmc_amd/diagnostics.py forms the covariance,
+ * the correlation and the highest-density levels of a contour plot from them).  The history is glabc_autocov's in both:
+ * [n_rows][theta_dim][stride] float32, columns n_chains .. stride - 1 never read; its base needs 4-byte alignment only.
+ *
+ * glabc_histogram2d: every pair p = (a, b) = (pairs[2p], pairs[2p + 1]) of coordinates has a table of n_bins^2 + 2 slots,
+ * counts[p * (n_bins^2 + 2) + slot] (device, uint64; the call ADDS, the caller zeroes).  pairs, lo and hi are HOST arrays.  Each of
+ * the two values of a draw (row t, chain c) is binned by glabc_histogram's rule on its own coordinate -- the same double
+ * arithmetic, scale = (double) n_bins / (hi - lo) formed on the host, x == hi in the last bin, every operation rounded once, no
+ * FMA -- and the draw adds one to
+ *     slot n_bins^2 + 1                  if either value is a NaN
+ *     slot n_bins^2                      otherwise, if either value is below its lo or above its hi
+ *     slot bin_a * n_bins + bin_b        otherwise
+ * (a, b) and (b, a) are both legal and each other's transposes; a pair may repeat, each occurrence has its own table.  The counts
+ * are integers: the same bits whatever the launch geometry.
+ *
+ * Refusals, in this order; a refused call launches nothing and writes nothing: a null pointer GLABC_ERR_NULL; theta_dim outside
+ * 1 .. GLABC_MAX_DIM GLABC_ERR_DIM; n_rows < 1, n_chains < 0, stride < n_chains, n_pairs outside 1 .. GLABC_MAX_PAIRS, a pair
+ * member outside 0 .. theta_dim - 1 or a == b, n_bins outside 1 .. GLABC_MAX_JOINT_BINS, and -- for a coordinate that a pair
+ * uses; the others' lo and hi are not looked at -- a lo or hi that is not finite or not lo < hi GLABC_ERR_ARG.  n_chains == 0
+ * returns GLABC_OK and writes nothing. */
+#define GLABC_MAX_PAIRS 28          /* GLABC_MAX_DIM (GLABC_MAX_DIM - 1) / 2 */
+#define GLABC_MAX_JOINT_BINS 128
+int glabc_histogram2d(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_pairs,
+                      const int32_t* pairs, int32_t n_bins, const double* lo, const double* hi, uint64_t* counts, void* stream);
+
+/* glabc_cross_moments: per chain, the means and the biased (1/n) covariance of every pair of coordinates.  The outputs are dense
+ * device arrays with output stride n_chains, the covariance as the packed upper triangle:
+ *     mean_out[j * n_chains + c]                          j < theta_dim, as glabc_autocov's
+ *     cov_out[q * n_chains + c]                           q = i * theta_dim - i (i - 1) / 2 + (j - i),   i <= j < theta_dim
+ * Numerical specification.  All arithmetic is IEEE double, every line one rounded operation in the stated order, no FMA.  With
+ * m and u_t per coordinate as in glabc_autocov:
+ *     A = 0.0;  for t = 0 .. n_rows - 1 ascending:  A = A + u_t,i * u_t,j;        cov = A / (double) n_rows
+ * so the diagonal entries are glabc_autocov's acov_0 bit for bit, and the result does not depend on the launch geometry.  A NaN
+ * or an infinity in a chain propagates as the lines say: into that chain's entries of the coordinates involved, nowhere else.
+ *
+ * Refusals, in this order; a refused call launches nothing and writes nothing: a null pointer GLABC_ERR_NULL; theta_dim outside
+ * 1 .. GLABC_MAX_DIM GLABC_ERR_DIM; n_rows < 1, n_chains < 0 or stride < n_chains GLABC_ERR_ARG.  n_chains == 0 returns GLABC_OK
+ * and writes nothing.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged by both: no struct changes. */
+int glabc_cross_moments(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, double* mean_out,
+                        double* cov_out, void* stream);
+
 /* ---- plain rejection ABC: prior draw -> simulation -> distance -> the Model's own acceptance, one fused kernel (csrc/glabc_abc.hip).
  * What picks a tolerance (a quantile of the prior-predictive distances), starts chains (the nearest draws) and samples the
  * samplers' target independently of them (glabcmcmc_amd/rejection.py).
