@@ -338,6 +338,62 @@ inline int check_abc_draws(const glabc_model* m, int64_t row0, const int64_t* id
     return check_abc_range(row0, ids, n, stride);
 }
 
+// ---- glabc_predictive_draws / glabc_predictive_counts: the Model a predictive draw is compiled for (check_abc_model's rules without
+// the prior, which is neither used nor examined), the history and the ids, in the order include/glabc.h lists the refusals; each
+// entry point adds what its own outputs ask
+inline int check_predictive_model(const glabc_model* m, int32_t theta_dim)
+{
+    if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
+    if (m->sim_kind == GLABC_SIM_GK && (m->theta_dim != 4 || m->y_dim != 8)) return GLABC_ERR_DIM;
+    if (m->sim_kind == GLABC_SIM_ABS_GAUSS && m->y_dim != m->theta_dim) return GLABC_ERR_DIM;
+    if (theta_dim != m->theta_dim) return GLABC_ERR_DIM;
+    if (m->sim_kind != GLABC_SIM_ABS_GAUSS && m->sim_kind != GLABC_SIM_GK) return GLABC_ERR_KIND;
+    return GLABC_OK;
+}
+
+// the last id of a call, id0 + (n_rows - 1) * id_step + n_chains - 1, must be an int64
+inline int check_predictive_range(int64_t n_rows, int64_t n_chains, int64_t stride, int64_t id0, int64_t id_step)
+{
+    if (n_rows < 1 || n_chains < 0 || stride < n_chains) return GLABC_ERR_ARG;
+    if (id0 < 0 || id_step < n_chains) return GLABC_ERR_ARG;
+    int64_t last;
+    if (__builtin_mul_overflow(n_rows - 1, id_step, &last) || __builtin_add_overflow(last, id0, &last) ||
+        __builtin_add_overflow(last, n_chains > 0 ? n_chains - 1 : 0, &last))
+        return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
+inline int check_predictive_draws(const glabc_model* m, const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains,
+                                  int64_t stride, int64_t id0, int64_t id_step, const float* y_out, int64_t y_stride, const float* dis_out,
+                                  int64_t dis_stride)
+{
+    if (!m || !history || (!y_out && !dis_out)) return GLABC_ERR_NULL;
+    if (int e = check_predictive_model(m, theta_dim)) return e;
+    if (n_rows < 1 || n_chains < 0 || stride < n_chains) return GLABC_ERR_ARG;
+    if ((y_out && y_stride < n_chains) || (dis_out && dis_stride < n_chains)) return GLABC_ERR_ARG;
+    return check_predictive_range(n_rows, n_chains, stride, id0, id_step);
+}
+
+inline int check_predictive_counts(const glabc_model* m, const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains,
+                                   int64_t stride, int64_t id0, int64_t id_step, int32_t n_bins, const double* lo, const double* hi,
+                                   const float* threshold, const uint64_t* counts, const uint64_t* tails, const uint32_t* extremes)
+{
+    if (!m || !history || (!counts && !tails && !extremes)) return GLABC_ERR_NULL;
+    if ((counts && (!lo || !hi)) || (tails && !threshold)) return GLABC_ERR_NULL;
+    if (int e = check_predictive_model(m, theta_dim)) return e;
+    if (int e = check_predictive_range(n_rows, n_chains, stride, id0, id_step)) return e;
+    const int n_stats = m->y_dim + 1;
+    if (counts) {
+        if (n_bins < 1 || n_bins > GLABC_MAX_PREDICTIVE_BINS) return GLABC_ERR_ARG;
+        for (int k = 0; k < n_stats; ++k)
+            if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || !(lo[k] < hi[k])) return GLABC_ERR_ARG;
+    }
+    if (tails)
+        for (int k = 0; k < n_stats; ++k)
+            if (threshold[k] != threshold[k]) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
 // ---- glabc_kde: what every entry point that reads a fitted KernelDensity asks of its descriptor (cum_q is glabc_kde_sample's and
 // glabc_smc_draws' alone and they ask for it themselves)
 inline int kde_check(const glabc_kde* k)

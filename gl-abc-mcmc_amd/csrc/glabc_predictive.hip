@@ -1,0 +1,336 @@
+// glabc_predictive.hip -- posterior predictive checks: glabc_predictive_draws and glabc_predictive_counts of include/glabc.h, which
+// holds the specification of a predictive draw and of the three integer tables.
+//
+// predictive_kernel<D, YD>.  The counting skeleton of glabc_joint.hip's joint_kernel around the draw of glabc_abc.h's abc_draws_kernel:
+// lanes run along the chain index, the work is cut into items of 64 chains x R rows (R = pred_rows(D): 16 / D rows, so about 16
+// loads are in flight per item) that the PRED_WAVES wavefronts of the gridDim.x workgroups take round-robin.  An item loads the
+// D row segments of its R rows, all issued together, every one through a buffer descriptor over exactly the segment's bytes: a
+// padding column, the bytes behind a ragged last segment and a row past the end cannot be read, whatever the base's alignment, and a
+// lane outside the segment stores and counts nothing.  Then, per lane and row: the Philox blocks and Box-Muller pairs of
+// abc_draws_kernel under the predictive key, model_simulate and model_discrepancy_rows of glabc_device.h -- the functions
+// glabc_model_simulate / glabc_model_discrepancy inline, which is what makes the bits agree with their composition.
+// Outputs.  Which are wanted is wave-uniform (a NULL pointer in the argument block), as in abc_draws_kernel:
+//   y, dis     plain stores in the history's layout (glabc_predictive_draws)
+//   counts     K = YD + 1 tables of n_bins + 3 uint32 counters in LDS (at most 9 x 1027 x 4 = 36 972 bytes: what a launch gets
+//              unasked), zeroed at the start, one LDS atomic per statistic and draw by glabc_histogram's double arithmetic (the
+//              object is built with -ffp-contract=off); at its end a workgroup adds its non-zero counters to `counts` with 64-bit
+//              integer atomics.  predictive_grid sizes the grid so that no workgroup counts 2^32 or more draws.
+//   tails      three ballots and population counts per statistic and row into wave-uniform counters, flushed once per wavefront; the
+//              NaN slot is the wavefront's draws less the three
+//   extremes   the smallest and largest key per lane, reduced across the wavefront at the end, one atomicMin / atomicMax per
+//              wavefront and statistic
+// Integer adds, minima and maxima commute: the tables are the same bits in every order and for every grid.
+// The by-value argument arrays are indexed by unrolled loop counters only, so the block stays in scalar registers;
+// profiles/predictive_kernel_resources.txt holds the compiler's resource report.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+
+#include "glabc_check.h"
+#include "glabc_device.h"
+#include "glabc_dispatch.h"
+#include "glabc_launch.h"
+#include "glabc_pack.h"
+
+namespace glabc {
+
+constexpr int PRED_LANES = 64;          // chains per item: one wavefront wide
+constexpr int PRED_WAVES = 8;           // wavefronts per workgroup, sharing one table of counters
+constexpr int PRED_LOADS = 16;          // loads in flight per item, as count_kernel's and joint_kernel's 16
+constexpr int PRED_CUS = 256;           // MI355X; sizes the grid only
+constexpr int PRED_PER_CU = 4;          // workgroups per CU: 32 wavefronts, and 4 x 36 972 bytes of LDS
+constexpr int64_t PRED_MAX_ITEMS_PER_WAVE = 1 << 18;     // x PRED_WAVES x 16 rows x PRED_LANES = 2^31 draws per workgroup
+
+// rows per item: 16, 8, 5, 4, 3, 2, 2, 2 at D = 1 .. 8
+constexpr int pred_rows(int D) { return PRED_LOADS / D; }
+
+template <int D, int YD>
+struct PredArgs {
+    StepArgs<D, YD> s;            // the Model as the samplers' kernels see it: simulator, y_obs
+    const float* hist;
+    int64_t n_rows, row_step, n_chains, stride;
+    int64_t id0, id_step;
+    uint32_t key_lo, key_hi;      // seed ^ GLABC_PREDICTIVE_KEY
+    float* y;                     // glabc_predictive_draws
+    float* dis;
+    int64_t y_stride, dis_stride;
+    unsigned long long* counts;   // glabc_predictive_counts
+    unsigned long long* tails;
+    uint32_t* extremes;
+    int32_t n_bins;
+    double lo[YD + 1], hi[YD + 1], scale[YD + 1];
+    float thr[YD + 1];
+};
+
+// the order-preserving key of glabc_key_counts (include/glabc.h)
+__device__ __forceinline__ uint32_t pred_key(float x)
+{
+    uint32_t u = __builtin_bit_cast(uint32_t, x);
+    if (x != x) return 0xFFFFFFFFu;
+    if (x == 0.0f) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// the slot of a value among the n_bins + 3 of its statistic: glabc_histogram's rule
+__device__ __forceinline__ int pred_slot(float xf, double lo, double hi, double scale, int n_bins)
+{
+    const double x = (double)xf;
+    if (x != x) return n_bins + 2;
+    if (x < lo) return n_bins;
+    if (x > hi) return n_bins + 1;
+    if (x == hi) return n_bins - 1;
+    const double u = (x - lo) * scale;                            // two rounded operations: -ffp-contract=off
+    const int b = (int)__builtin_floor(u);                        // 0 <= u <= n_bins (1 + 2^-52): inside int32
+    return b < n_bins - 1 ? b : n_bins - 1;
+}
+
+// element `lane` of the row segment at the wave-uniform address `row`: nothing behind its `bytes` bytes can be read
+__device__ __forceinline__ float load_segment(const float* row, int bytes, unsigned lane)
+{
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, bytes, 0x00020000);
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, lane * 4u, 0, 0));
+}
+
+template <int D, int YD>
+__global__ void __launch_bounds__(PRED_LANES* PRED_WAVES) predictive_kernel(const PredArgs<D, YD> a)
+{
+    constexpr int R = pred_rows(D), K = YD + 1;
+    extern __shared__ uint32_t table[];
+    const int n_bins = a.n_bins;
+    const int n_slots = a.counts ? K * (n_bins + 3) : 0;          // no counts: no LDS was asked for
+    const int tid = threadIdx.y * PRED_LANES + threadIdx.x;
+    for (int i = tid; i < n_slots; i += PRED_LANES * PRED_WAVES) table[i] = 0u;
+    __syncthreads();
+
+    const bool want_stats = a.counts || a.tails || a.extremes;
+    const bool want_dis = a.dis || want_stats;                   // else (y alone) the distance is not formed
+    uint32_t tail[K][3];                                          // wave-uniform: x < thr, x == thr, x > thr
+    uint32_t key_min[K], key_max[K];                              // per lane
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        tail[k][0] = tail[k][1] = tail[k][2] = 0u;
+        key_min[k] = 0xFFFFFFFFu, key_max[k] = 0u;
+    }
+    uint32_t n_live = 0u;                                         // wave-uniform: the draws this wavefront has made
+
+    const unsigned lane = threadIdx.x;
+    const int64_t n_segments = (a.n_chains + PRED_LANES - 1) / PRED_LANES;
+    const int64_t n_items = n_segments * ((a.n_rows + R - 1) / R);
+    const int64_t n_waves = (int64_t)gridDim.x * PRED_WAVES;
+    const int64_t wave = (int64_t)blockIdx.x * PRED_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+    for (int64_t item = wave; item < n_items; item += n_waves) {
+        const int64_t chain0 = item % n_segments * PRED_LANES;
+        const int64_t row0 = item / n_segments * R;
+        const int live = (int)(a.n_chains - chain0 < PRED_LANES ? a.n_chains - chain0 : PRED_LANES);          // lanes inside the segment
+        const int rows = (int)(a.n_rows - row0 < R ? a.n_rows - row0 : R);                                      // rows inside the history
+        const float* p = a.hist + row0 * a.row_step + chain0;
+        float x[R][D];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {                             // a row past the end: the last row's address and no bytes
+#pragma unroll
+            for (int j = 0; j < D; ++j) x[r][j] = load_segment(p + j * a.stride, r < rows ? 4 * live : 0, lane);
+            p += r + 1 < rows ? a.row_step : 0;
+        }
+        const bool inside = (int)lane < live;
+        const int64_t c = chain0 + lane;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (r < rows) {                                       // wave-uniform
+                const int64_t t = row0 + r;
+                const uint64_t id = (uint64_t)(a.id0 + t * a.id_step + c);
+                const uint32_t id_lo = (uint32_t)id, id_hi = (uint32_t)(id >> 32);
+
+                // y: glabc_model_simulate(eps = NULL) under the predictive key -- normal j is word pair (2j, 2j + 1) of the blocks (id, 0, b)
+                constexpr int ND = NoiseDim<YD>::value, NYB = (ND + 3) / 4;
+                float nrm[4 * NYB], eps[ND], theta[D], v[K];      // v: the statistics, y and then the distance
+#pragma unroll
+                for (int b = 0; b < NYB; ++b) {
+                    const glabc_u32x4 w = glabc_philox4x32_10(id_lo, id_hi, 0u, (uint32_t)b, a.key_lo, a.key_hi);
+                    glabc_normal_pair(w.v[0], w.v[1], &nrm[4 * b], &nrm[4 * b + 1]);
+                    glabc_normal_pair(w.v[2], w.v[3], &nrm[4 * b + 2], &nrm[4 * b + 3]);
+                }
+#pragma unroll
+                for (int j = 0; j < ND; ++j) eps[j] = nrm[j];
+#pragma unroll
+                for (int j = 0; j < D; ++j) theta[j] = x[r][j];
+                {
+                    float y[YD];
+                    model_simulate<D, YD>(a.s, theta, eps, y);
+                    if (a.y && inside) {
+#pragma unroll
+                        for (int j = 0; j < YD; ++j) a.y[(t * YD + j) * a.y_stride + c] = y[j];
+                    }
+#pragma unroll
+                    for (int j = 0; j < YD; ++j) v[j] = y[j];
+                    if (want_dis) v[YD] = model_discrepancy_rows<YD>(y, a.s.y_obs);
+                }
+                if (a.dis && inside) a.dis[t * a.dis_stride + c] = v[YD];
+                if (want_stats) n_live += (uint32_t)live;
+                if (a.counts) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        const int slot = pred_slot(v[k], a.lo[k], a.hi[k], a.scale[k], n_bins);      // below n_bins + 3
+                        if (inside) atomicAdd(&table[k * (n_bins + 3) + slot], 1u);
+                    }
+                }
+                if (a.tails) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        tail[k][0] += (uint32_t)__builtin_popcountll(__ballot(inside && v[k] < a.thr[k]));
+                        tail[k][1] += (uint32_t)__builtin_popcountll(__ballot(inside && v[k] == a.thr[k]));
+                        tail[k][2] += (uint32_t)__builtin_popcountll(__ballot(inside && v[k] > a.thr[k]));
+                    }
+                }
+                if (a.extremes) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        const uint32_t key = pred_key(v[k]);
+                        const bool counted = inside && key != 0xFFFFFFFFu;
+                        key_min[k] = counted && key < key_min[k] ? key : key_min[k];
+                        key_max[k] = counted && key > key_max[k] ? key : key_max[k];
+                    }
+                }
+            }
+        }
+    }
+
+    if (a.tails && lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const uint32_t n_nan = n_live - tail[k][0] - tail[k][1] - tail[k][2];
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+                if (tail[k][s]) atomicAdd(&a.tails[k * 4 + s], (unsigned long long)tail[k][s]);
+            if (n_nan) atomicAdd(&a.tails[k * 4 + 3], (unsigned long long)n_nan);
+        }
+    }
+    if (a.extremes) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            uint32_t lo = key_min[k], hi = key_max[k];
+#pragma unroll
+            for (int m = PRED_LANES / 2; m >= 1; m >>= 1) {
+                const uint32_t other_lo = (uint32_t)__shfl_xor((int)lo, m), other_hi = (uint32_t)__shfl_xor((int)hi, m);
+                lo = other_lo < lo ? other_lo : lo;
+                hi = other_hi > hi ? other_hi : hi;
+            }
+            if (lane == 0 && lo != 0xFFFFFFFFu) {                 // a wavefront that met a value that is no NaN
+                atomicMin(&a.extremes[2 * k], lo);
+                atomicMax(&a.extremes[2 * k + 1], hi);
+            }
+        }
+    }
+    if (!a.counts) return;                                        // wave-uniform, the whole grid alike
+    __syncthreads();
+    for (int i = tid; i < n_slots; i += PRED_LANES * PRED_WAVES) {
+        const uint32_t n = table[i];
+        if (n) atomicAdd(&a.counts[i], (unsigned long long)n);
+    }
+}
+
+// workgroups: enough to fill the part, no more than there are items, and -- the bound the uint32 counters (LDS, tails, n_live) need --
+// at least so many that a wavefront takes at most PRED_MAX_ITEMS_PER_WAVE items: a workgroup then counts at most
+// 2^18 x 8 x 16 x 64 = 2^31 draws between zeroing and flush
+inline unsigned predictive_grid(int64_t n_rows, int64_t n_chains, int rows_per_item)
+{
+    const int64_t n_items = ((n_chains + PRED_LANES - 1) / PRED_LANES) * ((n_rows + rows_per_item - 1) / rows_per_item);
+    int64_t g = PRED_CUS * PRED_PER_CU;
+    const int64_t most = (n_items + PRED_WAVES - 1) / PRED_WAVES;
+    if (g > most) g = most;
+    const int64_t least = (n_items + PRED_WAVES * PRED_MAX_ITEMS_PER_WAVE - 1) / (PRED_WAVES * PRED_MAX_ITEMS_PER_WAVE);
+    if (g < least) g = least;
+    return (unsigned)g;
+}
+
+struct PredCall {
+    const glabc_model* model;
+    const float* history;
+    int64_t n_rows, n_chains, stride;
+    uint64_t seed;
+    int64_t id0, id_step;
+    float* y;
+    float* dis;
+    int64_t y_stride, dis_stride;
+    int32_t n_bins;
+    const double* lo;
+    const double* hi;
+    const float* threshold;
+    uint64_t* counts;
+    uint64_t* tails;
+    uint32_t* extremes;
+};
+
+template <int D, int YD>
+inline int launch_predictive(const PredCall& c, hipStream_t s)
+{
+    constexpr int K = YD + 1;
+    glabc_chains none;
+    std::memset(&none, 0, sizeof none);
+    PredArgs<D, YD> a;
+    std::memset(&a, 0, sizeof a);
+    a.s = pack_args_rinv<D, YD>(c.model, nullptr, &c.model->prior, &none, nullptr, 0.0f);
+    a.hist = c.history;
+    a.n_rows = c.n_rows, a.row_step = (int64_t)D * c.stride, a.n_chains = c.n_chains, a.stride = c.stride;
+    a.id0 = c.id0, a.id_step = c.id_step;
+    const uint64_t key = c.seed ^ GLABC_PREDICTIVE_KEY;
+    a.key_lo = (uint32_t)key, a.key_hi = (uint32_t)(key >> 32);
+    a.y = c.y, a.dis = c.dis, a.y_stride = c.y_stride, a.dis_stride = c.dis_stride;
+    a.counts = (unsigned long long*)c.counts, a.tails = (unsigned long long*)c.tails, a.extremes = c.extremes;
+    a.n_bins = c.counts ? c.n_bins : 1;
+    for (int k = 0; k < K; ++k) {
+        a.lo[k] = c.counts ? c.lo[k] : 0.0, a.hi[k] = c.counts ? c.hi[k] : 1.0;
+        const double width = a.hi[k] - a.lo[k];
+        a.scale[k] = (double)a.n_bins / width;
+        a.thr[k] = c.tails ? c.threshold[k] : 0.0f;
+    }
+    const size_t lds_bytes = c.counts ? (size_t)K * (c.n_bins + 3) * sizeof(uint32_t) : 0;
+    const unsigned g = predictive_grid(c.n_rows, c.n_chains, pred_rows(D));
+    hipLaunchKernelGGL((predictive_kernel<D, YD>), dim3(g), dim3(PRED_LANES, PRED_WAVES), lds_bytes, s, a);
+    return launch_status();
+}
+
+inline int dispatch_predictive(const PredCall& c, hipStream_t s)
+{
+    if (c.model->sim_kind == GLABC_SIM_GK) return launch_predictive<4, 8>(c, s);
+    return dispatch_range<1, 8>(c.model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return launch_predictive<D, D>(c, s);
+    });
+}
+
+}  // namespace glabc
+
+using namespace glabc;
+
+extern "C" {
+
+__attribute__((visibility("default"))) int glabc_predictive_draws(const glabc_model* model, const float* history, int64_t n_rows,
+                                                                  int32_t theta_dim, int64_t n_chains, int64_t stride, uint64_t seed,
+                                                                  int64_t id0, int64_t id_step, float* y_out, int64_t y_stride,
+                                                                  float* dis_out, int64_t dis_stride, void* stream)
+{
+    if (int e = check_predictive_draws(model, history, n_rows, theta_dim, n_chains, stride, id0, id_step, y_out, y_stride, dis_out, dis_stride))
+        return e;
+    if (n_chains == 0) return GLABC_OK;
+    const PredCall c{model, history, n_rows, n_chains, stride, seed, id0, id_step, y_out, dis_out, y_stride, dis_stride,
+                     0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return dispatch_predictive(c, (hipStream_t)stream);
+}
+
+__attribute__((visibility("default"))) int glabc_predictive_counts(const glabc_model* model, const float* history, int64_t n_rows,
+                                                                   int32_t theta_dim, int64_t n_chains, int64_t stride, uint64_t seed,
+                                                                   int64_t id0, int64_t id_step, int32_t n_bins, const double* lo,
+                                                                   const double* hi, const float* threshold, uint64_t* counts,
+                                                                   uint64_t* tails, uint32_t* extremes, void* stream)
+{
+    if (int e = check_predictive_counts(model, history, n_rows, theta_dim, n_chains, stride, id0, id_step, n_bins, lo, hi, threshold, counts,
+                                        tails, extremes))
+        return e;
+    if (n_chains == 0) return GLABC_OK;
+    const PredCall c{model, history, n_rows, n_chains, stride, seed, id0, id_step, nullptr, nullptr, 0, 0,
+                     n_bins, lo, hi, threshold, counts, tails, extremes};
+    return dispatch_predictive(c, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -334,6 +334,10 @@ ENTRY_POINTS = {
     "glabc_cross_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_abc_draws": (C.c_int, [_P(Model), C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "glabc_predictive_draws": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "glabc_predictive_counts": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_smc_draws": (C.c_int, [_P(Model), _P(Kde), C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_rtc_compile_draws": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),

@@ -852,6 +852,64 @@ int glabc_cross_moments(const float* history, int64_t n_rows, int32_t theta_dim,
 int glabc_abc_draws(const glabc_model* model, uint64_t seed, int64_t row0, const int64_t* ids, int64_t n, int64_t stride,
                     float* theta_out, float* y_out, float* dis_out, uint8_t* accept_out, void* stream);
 
+/* ---- posterior predictive checks: a fresh simulation y_rep ~ p(y | theta) for every draw theta of a history, and integer summaries
+ * of y_rep and of its distance to y_obs, one fused kernel family (csrc/glabc_predictive.hip; glabcmcmc_amd/predictive.py forms the
+ * predictive p-values and histograms from them).  The history is glabc_autocov's: [n_rows][theta_dim][stride] float32, chain-major,
+ * columns n_chains .. stride - 1 never read; its base needs 4-byte alignment only; theta_dim must equal model->theta_dim.
+ *
+ * Specification of a predictive draw.  Draw (row t, chain c) has the 64-bit id  id = id0 + t * id_step + c  with id0 >= 0 and
+ * id_step >= n_chains, so the ids of a call are distinct, and slabs of chains (id0 + chain0) or slices of rows (id0 + row0 * id_step)
+ * address the very draws of the whole.  With id_lo / id_hi the two words of the id:
+ *     theta = history[t][:][c]
+ *     y     = glabc_model_simulate(model, theta, eps = NULL, seed ^ GLABC_PREDICTIVE_KEY, id): the Philox blocks
+ *             (seed ^ GLABC_PREDICTIVE_KEY; id_lo, id_hi, 0, b), b < ceil(y_dim / 4), Box-Muller pairs of words (2i, 2i + 1), as in
+ *             glabc_abc_draws; the key differs from both of that entry point's, so the predictive noise is no stream a sampler or the
+ *             rejection kernel used under the same seed
+ *     dis   = glabc_model_discrepancy(model, y)
+ * every line one rounded float32 operation per operator (no FMA: -ffp-contract=off).  The result depends on (model, the history's
+ * value, seed, id) only -- never on the launch geometry, nor on how rows and chains were cut into calls.  A NaN or an infinity in the
+ * history propagates as the lines say.  Models: those of glabc_abc_draws, GLABC_SIM_ABS_GAUSS with theta_dim == y_dim in
+ * 1 .. GLABC_MAX_DIM and GLABC_SIM_GK (4, 8); the prior is not used and not examined.
+ *
+ * glabc_predictive_draws materialises the draws (device arrays, float32):
+ *     y_out[(t * y_dim + j) * y_stride + c]   j < y_dim: the history's layout with its own stride      dis_out[t * dis_stride + c]
+ * Either may be NULL, not both; what only a NULL output needs is not computed.  Columns n_chains .. of either are never written.
+ *
+ * glabc_predictive_counts keeps the draws in registers and ADDS to integer tables (device arrays; the caller zeroes or initialises
+ * them, so slabs of chains and slices of rows accumulate into one).  There are K = y_dim + 1 statistics: statistic k < y_dim is y_k,
+ * statistic y_dim is dis.  Each of the three outputs may be NULL, not all of them.
+ *     counts[k * (n_bins + 3) + slot]   uint64.  glabc_histogram's rule on statistic k over [lo[k], hi[k]], the same double arithmetic:
+ *                                       scale = (double) n_bins / (hi[k] - lo[k]) on the host;  u = ((double) x - lo[k]) * scale,
+ *                                       b = floor(u);  NaN -> slot n_bins + 2;  x < lo -> slot n_bins;  x > hi -> slot n_bins + 1;
+ *                                       x == hi -> bin n_bins - 1;  otherwise bin min(b, n_bins - 1).  lo and hi are HOST arrays of K
+ *                                       doubles, looked at only when counts is not NULL, as n_bins in 1 .. GLABC_MAX_PREDICTIVE_BINS
+ *     tails[k * 4 + s]                  uint64.  x against threshold[k] (HOST array of K float32, looked at only when tails is not
+ *                                       NULL), compared in float32:  s = 0 for x < thr, 1 for x == thr, 2 for x > thr, 3 for a NaN x
+ *     extremes[k * 2 + {0, 1}]          uint32.  atomicMin / atomicMax of the order-preserving key of glabc_key_counts over the
+ *                                       statistic's values that are not NaN; the caller initialises the pair to 0xFFFFFFFF / 0
+ *                                       (what it still holds after a call: every value was a NaN)
+ * All three are integers: the same bits for every launch geometry and every order of the atomics.
+ *
+ * Refusals of both, in this order; a refused call launches nothing and writes nothing:
+ *   a NULL model or history, all outputs NULL, counts without lo or hi, tails without threshold   GLABC_ERR_NULL
+ *   theta_dim or y_dim of the Model outside 1 .. GLABC_MAX_DIM, GLABC_SIM_GK not (4, 8), GLABC_SIM_ABS_GAUSS with y_dim != theta_dim,
+ *   theta_dim != model->theta_dim                                                                GLABC_ERR_DIM
+ *   GLABC_SIM_USER or an unknown simulator kind                                                  GLABC_ERR_KIND
+ *   n_rows < 1, n_chains < 0, stride < n_chains; the stride of an output that is not NULL < n_chains; id0 < 0, id_step < n_chains,
+ *   or id0 + (n_rows - 1) * id_step + n_chains - 1 past int64; with counts: n_bins outside 1 .. GLABC_MAX_PREDICTIVE_BINS, a lo or
+ *   hi that is not finite or not lo < hi; with tails: a NaN threshold                            GLABC_ERR_ARG
+ * n_chains == 0 returns GLABC_OK and writes nothing.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no struct changes and no
+ * existing draw moves. */
+#define GLABC_PREDICTIVE_KEY 0xA0761D6478BD642Full
+#define GLABC_MAX_PREDICTIVE_BINS 1024
+int glabc_predictive_draws(const glabc_model* model, const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains,
+                           int64_t stride, uint64_t seed, int64_t id0, int64_t id_step, float* y_out, int64_t y_stride, float* dis_out,
+                           int64_t dis_stride, void* stream);
+int glabc_predictive_counts(const glabc_model* model, const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains,
+                            int64_t stride, uint64_t seed, int64_t id0, int64_t id_step, int32_t n_bins, const double* lo,
+                            const double* hi, const float* threshold, uint64_t* counts, uint64_t* tails, uint32_t* extremes,
+                            void* stream);
+
 /* ---- KernelDensity, the adaptive proposal of AGLMCMC (kernel_density.py:4-177) --------
  * A weighted Gaussian KDE over n_samples centres.  All arrays are device pointers; x is dimension-major.
  *
