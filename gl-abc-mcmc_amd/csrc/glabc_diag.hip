@@ -21,9 +21,9 @@
 //   last chunk:               a row past n_rows - 1 reads the last row again and every sum keeps its bits (a select, not a
 //                             product with zero: 0 * inf would be NaN where the specification has no term)
 //   last lag block:           sums of lags past max_lag are formed from rows inside the history and not stored
-// Loads.  A row segment is read through a buffer descriptor over exactly its bytes: one scalar base and one 32-bit lane offset
-// (with 64-bit per-lane pointers the compiler keeps an induction pointer per unrolled row in VGPRs, 4 x LAGS of them), and
-// nothing behind the segment -- a padding column, the next row -- can be read.  The row pointers advance by one row per load
+// Loads.  A row segment is read by glabc_history.h's load_segment, a buffer descriptor over exactly its bytes: one scalar base and
+// one 32-bit lane offset (with 64-bit per-lane pointers the compiler keeps an induction pointer per unrolled row in VGPRs,
+// 4 x LAGS of them), and nothing behind the segment can be read.  The row pointers advance by one row per load
 // for the same reason: LAGS multiples of the row step would be hoisted out of the loop and spill the scalar file.  The loads of
 // ROW_BATCH rows are issued together; a scheduling barrier behind every row keeps the compiler from hoisting the loads of the
 // whole chunk to its top, which spills.
@@ -36,6 +36,7 @@
 #include <utility>
 
 #include "glabc_check.h"
+#include "glabc_history.h"
 #include "glabc_launch.h"
 
 namespace glabc {
@@ -59,14 +60,6 @@ __global__ void __launch_bounds__(DIAG_LANES) mean_kernel(const float* __restric
     mean_out[j * n_chains + c] = s / (double)n_rows;
 }
 
-// element `lane` of the row segment at the wave-uniform address `row`: a buffer load through a descriptor of the segment's
-// row_bytes bytes, so the address is one scalar base and one 32-bit lane offset, and nothing behind the segment can be read
-__device__ __forceinline__ float load_row(const float* row, int row_bytes, unsigned lane)
-{
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, row_bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, lane * 4u, 0, 0));
-}
-
 // row I of a chunk: the trailing value enters the ring at w[I], the leading value meets the LAGS trailing values behind it.
 // FIRST: lag offset L has a partner from row L on; live == false (a row past the end, LAST chunks only): every sum keeps its bits
 template <bool FIRST, bool LAST, int I, int... L>
@@ -87,7 +80,7 @@ __device__ __forceinline__ void autocov_rows(const float*& ps, const float*& pt,
                                              std::integer_sequence<int, B...>)
 {
     float xs[sizeof...(B)], xt[sizeof...(B)];
-    ((xs[B] = load_row(ps, row_bytes, lane), xt[B] = load_row(pt, row_bytes, lane),
+    ((xs[B] = load_segment(ps, row_bytes, lane), xt[B] = load_segment(pt, row_bytes, lane),
       ps += !LAST || I0 + B + 1 < rows_left ? row_step : 0, pt += !LAST || I0 + B + 1 < rows_left ? row_step : 0), ...);
     (autocov_row<FIRST, LAST, I0 + B>(xs[B], xt[B], I0 + B < rows_left, m, acc, w, std::make_integer_sequence<int, LAGS>{}), ...);
 }

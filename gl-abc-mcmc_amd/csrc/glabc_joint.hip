@@ -1,17 +1,13 @@
 // glabc_joint.hip -- the joint posterior of a chain-major history: pair histograms (glabc_histogram2d) and per-chain cross moments
 // (glabc_cross_moments) of include/glabc.h, which holds both specifications.
 //
-// joint_kernel.  The counting skeleton of glabc_quant.hip's count_kernel with a pair of coordinates where that has one: lanes run
-// along the chain index, blockIdx.y is the pair, a pair's work is cut into items of 64 chains x JOINT_ROWS rows that the
-// JOINT_WAVES wavefronts of the gridDim.x workgroups take round-robin.  An item loads the row segments of both coordinates, all
-// 2 x JOINT_ROWS loads issued together, every one through a buffer descriptor over exactly the segment's bytes: a padding column,
-// the bytes behind a ragged last segment and a row past the end cannot be read, whatever the base's alignment, and a lane outside
-// the segment counts nothing.  Each value is binned on its own axis by glabc_histogram's double arithmetic (axis_bin; the object
-// is built with -ffp-contract=off) and the two bins make the slot.
-// Counters.  uint32 in LDS, n_bins^2 + 2 of them, zeroed at the start; at its end a workgroup adds its non-zero counters to `counts`
-// with 64-bit integer atomics, so the table is the same bits in every order and for every grid.  joint_grid sizes the grid so
-// that no workgroup counts 2^32 or more draws.  At 128 bins the table is 65 544 bytes: past what a launch gets unasked, so the
-// launcher has the size granted (glabc_lds_grant.h) as the lane-group and the flow launchers do; two workgroups share a CU then.
+// joint_kernel.  glabc_quant.hip's count_kernel with a pair of coordinates where that has one: lanes run along the chain index,
+// blockIdx.y is the pair; the walk over items of 64 chains x JOINT_ROWS rows, the guarded loads, the uint32 table in LDS, the grid
+// rule and glabc_histogram's bin arithmetic are glabc_history.h's, which argues what cannot be read, that a slot is inside the table
+// and that no counter wraps.  An item loads the row segments of both coordinates, all 2 x JOINT_ROWS loads issued together, and a
+// lane outside the segment counts nothing.  Each value is binned on its own axis (axis_bin) and the two bins make the slot: n_bins^2 + 2
+// counters.  At 128 bins the table is 65 544 bytes: past what a launch gets unasked, so the launcher has the size granted
+// (glabc_lds_grant.h) as the lane-group and the flow launchers do; two workgroups share a CU then.
 // Contention.  One LDS atomic per draw.  A grid of bins spreads a posterior over far more counters than a level-0 digit table
 // does: folding the run of equal slots along an item's rows into one add (count_kernel's COUNT_RUNS) was measured and did not
 // pay, so it is not here.
@@ -30,18 +26,15 @@
 
 #include "glabc_check.h"
 #include "glabc_dispatch.h"
+#include "glabc_history.h"
 #include "glabc_launch.h"
 #include "glabc_lds_grant.h"
 
 namespace glabc {
 
-constexpr int JOINT_LANES = 64;         // chains per item: one wavefront wide
-constexpr int JOINT_WAVES = 8;          // wavefronts per workgroup, sharing one table of counters
 constexpr int JOINT_ROWS = 8;           // rows per item: the 16 loads of both coordinates in flight together, as count_kernel's 16
                                         // (16 rows are 32 descriptors, more than the scalar file holds without spilling)
-constexpr int JOINT_CUS = 256;          // MI355X; sizes the grid only
-constexpr int64_t JOINT_LDS_PER_CU = 160 * 1024;
-constexpr int64_t JOINT_MAX_ITEMS_PER_WAVE = 1 << 19;    // x JOINT_WAVES x JOINT_ROWS x JOINT_LANES = 2^31 draws per workgroup
+constexpr int64_t JOINT_MAX_ITEMS_PER_WAVE = 1 << 19;    // x HISTORY_WAVES x JOINT_ROWS x HISTORY_LANES = 2^31 draws per workgroup
 
 constexpr int AXIS_OUTSIDE = -1, AXIS_NAN = -2;
 
@@ -51,20 +44,14 @@ struct JointSlots {
     uint8_t a[GLABC_MAX_PAIRS], b[GLABC_MAX_PAIRS];
 };
 
-struct Axis {
-    double lo, hi, scale;
-    // the bin of a value on this axis, glabc_histogram's rule; AXIS_OUTSIDE below lo or above hi, AXIS_NAN
-    __device__ int bin(float xf, int n_bins) const
-    {
-        const double x = (double)xf;
-        if (x != x) return AXIS_NAN;
-        if (x < lo || x > hi) return AXIS_OUTSIDE;
-        if (x == hi) return n_bins - 1;
-        const double u = (x - lo) * scale;                        // two rounded operations: -ffp-contract=off
-        const int b = (int)__builtin_floor(u);                    // 0 <= u <= n_bins (1 + 2^-52): inside int32
-        return b < n_bins - 1 ? b : n_bins - 1;
-    }
-};
+// the bin of a value on an axis, glabc_histogram's rule; AXIS_OUTSIDE below lo or above hi, AXIS_NAN
+__device__ __forceinline__ int axis_bin(float xf, const BinAxis& a, int n_bins)
+{
+    const double x = (double)xf;
+    if (x != x) return AXIS_NAN;
+    if (x < a.lo || x > a.hi) return AXIS_OUTSIDE;
+    return bin_inside(x, a, n_bins);
+}
 
 // a NaN on either axis before a value outside on either axis before the cell
 __device__ __forceinline__ int joint_slot(int bin_a, int bin_b, int n_bins)
@@ -74,81 +61,54 @@ __device__ __forceinline__ int joint_slot(int bin_a, int bin_b, int n_bins)
     return least >= 0 ? bin_a * n_bins + bin_b : least == AXIS_NAN ? cells + 1 : cells;
 }
 
-// element `lane` of the row segment at the wave-uniform address `row`: nothing behind its `bytes` bytes can be read
-__device__ __forceinline__ float load_segment(const float* row, int bytes, unsigned lane)
-{
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, lane * 4u, 0, 0));
-}
-
-// slot < 0: nothing to add.  The table has n_bins^2 + 2 counters and joint_slot returns an index below that
-__device__ __forceinline__ void lds_add(uint32_t* table, int slot, uint32_t n)
-{
-    if (slot >= 0) atomicAdd(&table[slot], n);
-}
-
-__global__ void __launch_bounds__(JOINT_LANES* JOINT_WAVES)
+__global__ void __launch_bounds__(HISTORY_LANES* HISTORY_WAVES)
     joint_kernel(const float* __restrict__ hist, int64_t n_rows, int64_t row_step, int64_t n_chains, int64_t stride, const JointSlots slots,
                  unsigned long long* __restrict__ counts)
 {
     extern __shared__ uint32_t table[];
     const int n_bins = slots.n_bins;
     const int n_slots = n_bins * n_bins + 2;
-    const int tid = threadIdx.y * JOINT_LANES + threadIdx.x;
-    for (int i = tid; i < n_slots; i += JOINT_LANES * JOINT_WAVES) table[i] = 0u;
-    __syncthreads();
+    table_zero(table, n_slots);
 
     const int pair = blockIdx.y;
     const int ja = slots.a[pair], jb = slots.b[pair];
-    const Axis axis_a{slots.lo[ja], slots.hi[ja], slots.scale[ja]}, axis_b{slots.lo[jb], slots.hi[jb], slots.scale[jb]};
+    const BinAxis axis_a{slots.lo[ja], slots.hi[ja], slots.scale[ja]}, axis_b{slots.lo[jb], slots.hi[jb], slots.scale[jb]};
     const unsigned lane = threadIdx.x;
-    const int64_t n_segments = (n_chains + JOINT_LANES - 1) / JOINT_LANES;
-    const int64_t n_items = n_segments * ((n_rows + JOINT_ROWS - 1) / JOINT_ROWS);
-    const int64_t n_waves = (int64_t)gridDim.x * JOINT_WAVES;
-    const int64_t wave = (int64_t)blockIdx.x * JOINT_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.y);
-    for (int64_t item = wave; item < n_items; item += n_waves) {
-        const int64_t chain0 = item % n_segments * JOINT_LANES;
-        const int64_t row0 = item / n_segments * JOINT_ROWS;
-        const int live = (int)(n_chains - chain0 < JOINT_LANES ? n_chains - chain0 : JOINT_LANES);           // lanes inside the segment
-        const int rows = (int)(n_rows - row0 < JOINT_ROWS ? n_rows - row0 : JOINT_ROWS);                       // rows inside the history
-        const float* pa = hist + row0 * row_step + ja * stride + chain0;
-        const float* pb = hist + row0 * row_step + jb * stride + chain0;
+    const Walk<JOINT_ROWS> walk(n_rows, n_chains);
+    for (int64_t item = walk.first; item < walk.n_items; item += walk.n_waves) {
+        const Item it = walk.item(item);
+        const float* pa = hist + it.row0 * row_step + ja * stride + it.chain0;
+        const float* pb = hist + it.row0 * row_step + jb * stride + it.chain0;
         float xa[JOINT_ROWS], xb[JOINT_ROWS];
 #pragma unroll
-        for (int r = 0; r < JOINT_ROWS; ++r) {                    // a row past the end: the last row's address and no bytes
-            xa[r] = load_segment(pa, r < rows ? 4 * live : 0, lane);
-            xb[r] = load_segment(pb, r < rows ? 4 * live : 0, lane);
-            pa += r + 1 < rows ? row_step : 0;
-            pb += r + 1 < rows ? row_step : 0;
+        for (int r = 0; r < JOINT_ROWS; ++r) {
+            xa[r] = load_segment(pa, it.bytes(r), lane);
+            xb[r] = load_segment(pb, it.bytes(r), lane);
+            pa += it.step(r, row_step);
+            pb += it.step(r, row_step);
         }
-        const bool inside = (int)lane < live;
+        const bool inside = (int)lane < it.live;
 #pragma unroll
         for (int r = 0; r < JOINT_ROWS; ++r)
-            lds_add(table, inside && r < rows ? joint_slot(axis_a.bin(xa[r], n_bins), axis_b.bin(xb[r], n_bins), n_bins) : -1, 1u);
+            lds_add(table, inside && r < it.rows ? joint_slot(axis_bin(xa[r], axis_a, n_bins), axis_bin(xb[r], axis_b, n_bins), n_bins) : -1, 1u);
     }
-    __syncthreads();
-    unsigned long long* out = counts + (int64_t)pair * n_slots;
-    for (int i = tid; i < n_slots; i += JOINT_LANES * JOINT_WAVES) {
-        const uint32_t c = table[i];
-        if (c) atomicAdd(&out[i], (unsigned long long)c);
-    }
+    table_flush(table, n_slots, counts + (int64_t)pair * n_slots);
 }
 
-// workgroups per pair: enough to fill the part (as many workgroups per CU as its LDS and its 32 wavefronts hold), no more than
-// there are items, and -- the bound the uint32 counters need -- at least so many that a wavefront takes at most
-// JOINT_MAX_ITEMS_PER_WAVE items: a workgroup then counts at most 2^19 x 8 x 8 x 64 = 2^31 draws between zeroing and flush
-inline unsigned joint_grid(int64_t n_rows, int32_t n_pairs, int64_t n_chains, size_t lds_bytes)
+// workgroups per pair (history_grid): the part's fill is shared among the n_pairs pairs of gridDim.y
+constexpr unsigned joint_grid(int64_t n_rows, int32_t n_pairs, int64_t n_chains, size_t lds_bytes)
 {
-    const int64_t n_items = ((n_chains + JOINT_LANES - 1) / JOINT_LANES) * ((n_rows + JOINT_ROWS - 1) / JOINT_ROWS);
-    int64_t per_cu = JOINT_LDS_PER_CU / (int64_t)lds_bytes;
-    if (per_cu > 32 / JOINT_WAVES) per_cu = 32 / JOINT_WAVES;
-    int64_t g = (JOINT_CUS * per_cu + n_pairs - 1) / n_pairs;
-    const int64_t most = (n_items + JOINT_WAVES - 1) / JOINT_WAVES;
-    if (g > most) g = most;
-    const int64_t least = (n_items + JOINT_WAVES * JOINT_MAX_ITEMS_PER_WAVE - 1) / (JOINT_WAVES * JOINT_MAX_ITEMS_PER_WAVE);
-    if (g < least) g = least;
-    return (unsigned)g;
+    return history_grid(history_items(n_rows, n_chains, JOINT_ROWS), HISTORY_WAVES, JOINT_MAX_ITEMS_PER_WAVE,
+                        (HISTORY_CUS * workgroups_per_cu(lds_bytes) + n_pairs - 1) / n_pairs);
 }
+// ... pinned at what joint_grid's own arithmetic gave before it called history_grid
+static_assert(joint_grid(1, 1, 1, 12) == 1 && joint_grid(8, 28, 64, 65544) == 1 && joint_grid(8, 1, 7 * 64, 4104) == 1 &&
+                  joint_grid(8, 1, 9 * 64, 4104) == 2, "one item, HISTORY_WAVES - 1 and + 1 items");
+static_assert(joint_grid(1 << 20, 1, 65536, 65544) == 512 && joint_grid(1 << 20, 28, 65536, 65544) == 32, "128 bins, the largest table");
+static_assert(joint_grid(1 << 20, 1, 65536, 4104) == 1024 && joint_grid(1 << 20, 28, 65536, 4104) == 37, "32 bins, 1 and 28 pairs");
+static_assert(joint_grid(1 << 20, 3, 65536, 40008) == 342 && joint_grid(1 << 20, 3, 65536, 53832) == 256 &&
+                  joint_grid(1 << 20, 3, 65536, 54764) == 171, "100, 116 and 117 bins: four, three and two workgroups per CU");
+static_assert(joint_grid(1 << 18, 28, 1 << 20, 65544) == 128 && joint_grid(1 << 18, 1, 1 << 24, 4104) == 2048, "the counters' bound wins");
 
 inline int launch_joint(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_pairs,
                         const int32_t* pairs, int32_t n_bins, const double* lo, const double* hi, uint64_t* counts, hipStream_t s)
@@ -161,16 +121,15 @@ inline int launch_joint(const float* history, int64_t n_rows, int32_t theta_dim,
     }
     for (int q = 0; q < 2 * n_pairs; ++q) {
         const int c = pairs[q];
-        j.lo[c] = lo[c], j.hi[c] = hi[c];
-        const double width = j.hi[c] - j.lo[c];
-        j.scale[c] = (double)n_bins / width;
+        const BinAxis a = bin_axis(lo[c], hi[c], n_bins);
+        j.lo[c] = a.lo, j.hi[c] = a.hi, j.scale[c] = a.scale;
     }
     j.n_bins = n_bins;
     const size_t lds_bytes = ((size_t)n_bins * n_bins + 2) * sizeof(uint32_t);
     static LdsGrant grant;                               // per device
     if (!grant_dynamic_lds(grant, (const void*)joint_kernel, lds_bytes)) return GLABC_ERR_LAUNCH;
     const unsigned g = joint_grid(n_rows, n_pairs, n_chains, lds_bytes);
-    hipLaunchKernelGGL(joint_kernel, dim3(g, n_pairs), dim3(JOINT_LANES, JOINT_WAVES), lds_bytes, s, history, n_rows,
+    hipLaunchKernelGGL(joint_kernel, dim3(g, n_pairs), dim3(HISTORY_LANES, HISTORY_WAVES), lds_bytes, s, history, n_rows,
                        (int64_t)theta_dim * stride, n_chains, stride, j, (unsigned long long*)counts);
     return launch_status();
 }

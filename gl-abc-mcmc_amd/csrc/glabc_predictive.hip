@@ -1,20 +1,17 @@
 // glabc_predictive.hip -- posterior predictive checks: glabc_predictive_draws and glabc_predictive_counts of include/glabc.h, which
 // holds the specification of a predictive draw and of the three integer tables.
 //
-// predictive_kernel<D, YD>.  The counting skeleton of glabc_joint.hip's joint_kernel around the draw of glabc_abc.h's abc_draws_kernel:
-// lanes run along the chain index, the work is cut into items of 64 chains x R rows (R = pred_rows(D): 16 / D rows, so about 16
-// loads are in flight per item) that the PRED_WAVES wavefronts of the gridDim.x workgroups take round-robin.  An item loads the
-// D row segments of its R rows, all issued together, every one through a buffer descriptor over exactly the segment's bytes: a
-// padding column, the bytes behind a ragged last segment and a row past the end cannot be read, whatever the base's alignment, and a
-// lane outside the segment stores and counts nothing.  Then, per lane and row: the Philox blocks and Box-Muller pairs of
-// abc_draws_kernel under the predictive key, model_simulate and model_discrepancy_rows of glabc_device.h -- the functions
-// glabc_model_simulate / glabc_model_discrepancy inline, which is what makes the bits agree with their composition.
+// predictive_kernel<D, YD>.  glabc_joint.hip's joint_kernel around the draw of glabc_abc.h's abc_draws_kernel: lanes run along the
+// chain index; the walk over items of 64 chains x R rows (R = pred_rows(D): 16 / D rows, so about 16 loads are in flight per item),
+// the guarded loads, the uint32 table in LDS, the grid rule, the key and glabc_histogram's bin arithmetic are glabc_history.h's, which
+// argues what cannot be read, that a slot is inside the table and that no counter wraps.  An item loads the D row segments of its R
+// rows, all issued together; a lane outside the segment stores and counts nothing.  Then, per lane and row: the Philox blocks and
+// Box-Muller pairs of abc_draws_kernel under the predictive key, model_simulate and model_discrepancy_rows of glabc_device.h -- the
+// functions glabc_model_simulate / glabc_model_discrepancy inline, which is what makes the bits agree with their composition.
 // Outputs.  Which are wanted is wave-uniform (a NULL pointer in the argument block), as in abc_draws_kernel:
 //   y, dis     plain stores in the history's layout (glabc_predictive_draws)
 //   counts     K = YD + 1 tables of n_bins + 3 uint32 counters in LDS (at most 9 x 1027 x 4 = 36 972 bytes: what a launch gets
-//              unasked), zeroed at the start, one LDS atomic per statistic and draw by glabc_histogram's double arithmetic (the
-//              object is built with -ffp-contract=off); at its end a workgroup adds its non-zero counters to `counts` with 64-bit
-//              integer atomics.  predictive_grid sizes the grid so that no workgroup counts 2^32 or more draws.
+//              unasked), one LDS atomic per statistic and draw
 //   tails      three ballots and population counts per statistic and row into wave-uniform counters, flushed once per wavefront; the
 //              NaN slot is the wavefront's draws less the three
 //   extremes   the smallest and largest key per lane, reduced across the wavefront at the end, one atomicMin / atomicMax per
@@ -30,17 +27,14 @@
 #include "glabc_check.h"
 #include "glabc_device.h"
 #include "glabc_dispatch.h"
+#include "glabc_history.h"
 #include "glabc_launch.h"
 #include "glabc_pack.h"
 
 namespace glabc {
 
-constexpr int PRED_LANES = 64;          // chains per item: one wavefront wide
-constexpr int PRED_WAVES = 8;           // wavefronts per workgroup, sharing one table of counters
 constexpr int PRED_LOADS = 16;          // loads in flight per item, as count_kernel's and joint_kernel's 16
-constexpr int PRED_CUS = 256;           // MI355X; sizes the grid only
-constexpr int PRED_PER_CU = 4;          // workgroups per CU: 32 wavefronts, and 4 x 36 972 bytes of LDS
-constexpr int64_t PRED_MAX_ITEMS_PER_WAVE = 1 << 18;     // x PRED_WAVES x 16 rows x PRED_LANES = 2^31 draws per workgroup
+constexpr int64_t PRED_MAX_ITEMS_PER_WAVE = 1 << 18;     // x HISTORY_WAVES x 16 rows x HISTORY_LANES = 2^31 draws per workgroup
 
 // rows per item: 16, 8, 5, 4, 3, 2, 2, 2 at D = 1 .. 8
 constexpr int pred_rows(int D) { return PRED_LOADS / D; }
@@ -63,44 +57,15 @@ struct PredArgs {
     float thr[YD + 1];
 };
 
-// the order-preserving key of glabc_key_counts (include/glabc.h)
-__device__ __forceinline__ uint32_t pred_key(float x)
-{
-    uint32_t u = __builtin_bit_cast(uint32_t, x);
-    if (x != x) return 0xFFFFFFFFu;
-    if (x == 0.0f) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// the slot of a value among the n_bins + 3 of its statistic: glabc_histogram's rule
-__device__ __forceinline__ int pred_slot(float xf, double lo, double hi, double scale, int n_bins)
-{
-    const double x = (double)xf;
-    if (x != x) return n_bins + 2;
-    if (x < lo) return n_bins;
-    if (x > hi) return n_bins + 1;
-    if (x == hi) return n_bins - 1;
-    const double u = (x - lo) * scale;                            // two rounded operations: -ffp-contract=off
-    const int b = (int)__builtin_floor(u);                        // 0 <= u <= n_bins (1 + 2^-52): inside int32
-    return b < n_bins - 1 ? b : n_bins - 1;
-}
-
-// element `lane` of the row segment at the wave-uniform address `row`: nothing behind its `bytes` bytes can be read
-__device__ __forceinline__ float load_segment(const float* row, int bytes, unsigned lane)
-{
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, lane * 4u, 0, 0));
-}
-
 template <int D, int YD>
-__global__ void __launch_bounds__(PRED_LANES* PRED_WAVES) predictive_kernel(const PredArgs<D, YD> a)
+__global__ void __launch_bounds__(HISTORY_LANES* HISTORY_WAVES) predictive_kernel(const PredArgs<D, YD> a)
 {
     constexpr int R = pred_rows(D), K = YD + 1;
     extern __shared__ uint32_t table[];
     const int n_bins = a.n_bins;
     const int n_slots = a.counts ? K * (n_bins + 3) : 0;          // no counts: no LDS was asked for
-    const int tid = threadIdx.y * PRED_LANES + threadIdx.x;
-    for (int i = tid; i < n_slots; i += PRED_LANES * PRED_WAVES) table[i] = 0u;
+    // table_zero's text, not a call of it, which changes the scalar code around the select above (profiles/history_header_device_code.txt)
+    for (int i = threadIdx.y * HISTORY_LANES + threadIdx.x; i < n_slots; i += HISTORY_LANES * HISTORY_WAVES) table[i] = 0u;
     __syncthreads();
 
     const bool want_stats = a.counts || a.tails || a.extremes;
@@ -115,29 +80,23 @@ __global__ void __launch_bounds__(PRED_LANES* PRED_WAVES) predictive_kernel(cons
     uint32_t n_live = 0u;                                         // wave-uniform: the draws this wavefront has made
 
     const unsigned lane = threadIdx.x;
-    const int64_t n_segments = (a.n_chains + PRED_LANES - 1) / PRED_LANES;
-    const int64_t n_items = n_segments * ((a.n_rows + R - 1) / R);
-    const int64_t n_waves = (int64_t)gridDim.x * PRED_WAVES;
-    const int64_t wave = (int64_t)blockIdx.x * PRED_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.y);
-    for (int64_t item = wave; item < n_items; item += n_waves) {
-        const int64_t chain0 = item % n_segments * PRED_LANES;
-        const int64_t row0 = item / n_segments * R;
-        const int live = (int)(a.n_chains - chain0 < PRED_LANES ? a.n_chains - chain0 : PRED_LANES);          // lanes inside the segment
-        const int rows = (int)(a.n_rows - row0 < R ? a.n_rows - row0 : R);                                      // rows inside the history
-        const float* p = a.hist + row0 * a.row_step + chain0;
+    const Walk<R> walk(a.n_rows, a.n_chains);
+    for (int64_t item = walk.first; item < walk.n_items; item += walk.n_waves) {
+        const Item it = walk.item(item);
+        const float* p = a.hist + it.row0 * a.row_step + it.chain0;
         float x[R][D];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {                             // a row past the end: the last row's address and no bytes
+        for (int r = 0; r < R; ++r) {
 #pragma unroll
-            for (int j = 0; j < D; ++j) x[r][j] = load_segment(p + j * a.stride, r < rows ? 4 * live : 0, lane);
-            p += r + 1 < rows ? a.row_step : 0;
+            for (int j = 0; j < D; ++j) x[r][j] = load_segment(p + j * a.stride, it.bytes(r), lane);
+            p += it.step(r, a.row_step);
         }
-        const bool inside = (int)lane < live;
-        const int64_t c = chain0 + lane;
+        const bool inside = (int)lane < it.live;
+        const int64_t c = it.chain0 + lane;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if (r < rows) {                                       // wave-uniform
-                const int64_t t = row0 + r;
+            if (r < it.rows) {                                    // wave-uniform
+                const int64_t t = it.row0 + r;
                 const uint64_t id = (uint64_t)(a.id0 + t * a.id_step + c);
                 const uint32_t id_lo = (uint32_t)id, id_hi = (uint32_t)(id >> 32);
 
@@ -166,11 +125,11 @@ __global__ void __launch_bounds__(PRED_LANES* PRED_WAVES) predictive_kernel(cons
                     if (want_dis) v[YD] = model_discrepancy_rows<YD>(y, a.s.y_obs);
                 }
                 if (a.dis && inside) a.dis[t * a.dis_stride + c] = v[YD];
-                if (want_stats) n_live += (uint32_t)live;
+                if (want_stats) n_live += (uint32_t)it.live;
                 if (a.counts) {
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
-                        const int slot = pred_slot(v[k], a.lo[k], a.hi[k], a.scale[k], n_bins);      // below n_bins + 3
+                        const int slot = hist_slot(v[k], BinAxis{a.lo[k], a.hi[k], a.scale[k]}, n_bins);      // below n_bins + 3
                         if (inside) atomicAdd(&table[k * (n_bins + 3) + slot], 1u);
                     }
                 }
@@ -185,7 +144,7 @@ __global__ void __launch_bounds__(PRED_LANES* PRED_WAVES) predictive_kernel(cons
                 if (a.extremes) {
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
-                        const uint32_t key = pred_key(v[k]);
+                        const uint32_t key = float_key(v[k]);
                         const bool counted = inside && key != 0xFFFFFFFFu;
                         key_min[k] = counted && key < key_min[k] ? key : key_min[k];
                         key_max[k] = counted && key > key_max[k] ? key : key_max[k];
@@ -210,7 +169,7 @@ __global__ void __launch_bounds__(PRED_LANES* PRED_WAVES) predictive_kernel(cons
         for (int k = 0; k < K; ++k) {
             uint32_t lo = key_min[k], hi = key_max[k];
 #pragma unroll
-            for (int m = PRED_LANES / 2; m >= 1; m >>= 1) {
+            for (int m = HISTORY_LANES / 2; m >= 1; m >>= 1) {
                 const uint32_t other_lo = (uint32_t)__shfl_xor((int)lo, m), other_hi = (uint32_t)__shfl_xor((int)hi, m);
                 lo = other_lo < lo ? other_lo : lo;
                 hi = other_hi > hi ? other_hi : hi;
@@ -222,26 +181,23 @@ __global__ void __launch_bounds__(PRED_LANES* PRED_WAVES) predictive_kernel(cons
         }
     }
     if (!a.counts) return;                                        // wave-uniform, the whole grid alike
-    __syncthreads();
-    for (int i = tid; i < n_slots; i += PRED_LANES * PRED_WAVES) {
-        const uint32_t n = table[i];
-        if (n) atomicAdd(&a.counts[i], (unsigned long long)n);
-    }
+    table_flush(table, n_slots, a.counts);
 }
 
-// workgroups: enough to fill the part, no more than there are items, and -- the bound the uint32 counters (LDS, tails, n_live) need --
-// at least so many that a wavefront takes at most PRED_MAX_ITEMS_PER_WAVE items: a workgroup then counts at most
-// 2^18 x 8 x 16 x 64 = 2^31 draws between zeroing and flush
-inline unsigned predictive_grid(int64_t n_rows, int64_t n_chains, int rows_per_item)
+// workgroups (history_grid); its bound on a wavefront's items is what the uint32 tails and n_live need too
+constexpr unsigned predictive_grid(int64_t n_rows, int64_t n_chains, int rows_per_item, size_t lds_bytes)
 {
-    const int64_t n_items = ((n_chains + PRED_LANES - 1) / PRED_LANES) * ((n_rows + rows_per_item - 1) / rows_per_item);
-    int64_t g = PRED_CUS * PRED_PER_CU;
-    const int64_t most = (n_items + PRED_WAVES - 1) / PRED_WAVES;
-    if (g > most) g = most;
-    const int64_t least = (n_items + PRED_WAVES * PRED_MAX_ITEMS_PER_WAVE - 1) / (PRED_WAVES * PRED_MAX_ITEMS_PER_WAVE);
-    if (g < least) g = least;
-    return (unsigned)g;
+    return history_grid(history_items(n_rows, n_chains, rows_per_item), HISTORY_WAVES, PRED_MAX_ITEMS_PER_WAVE,
+                        HISTORY_CUS * workgroups_per_cu(lds_bytes));
 }
+// ... pinned at what predictive_grid's own arithmetic gave before it called history_grid (four workgroups per CU, whatever the table)
+static_assert(predictive_grid(1, 1, 16, 0) == 1 && predictive_grid(2, 64, 2, 36972) == 1 && predictive_grid(16, 7 * 64, 16, 16) == 1 &&
+                  predictive_grid(16, 9 * 64, 16, 16) == 2, "one item, HISTORY_WAVES - 1 and + 1 items");
+static_assert(predictive_grid(1 << 20, 65536, 16, 36972) == 1024 && predictive_grid(1 << 20, 65536, 2, 36972) == 1024 &&
+                  predictive_grid(1 << 20, 65536, 5, 0) == 1024 && predictive_grid(1 << 20, 65536, 4, 144) == 1024,
+              "theta_dim 1 and 8 with the largest table, no table, the smallest");
+static_assert(predictive_grid(1 << 19, 1ll << 26, 16, 36972) == 16384 && predictive_grid(1 << 16, 1ll << 26, 2, 0) == 16384,
+              "the counters' bound wins");
 
 struct PredCall {
     const glabc_model* model;
@@ -279,14 +235,13 @@ inline int launch_predictive(const PredCall& c, hipStream_t s)
     a.counts = (unsigned long long*)c.counts, a.tails = (unsigned long long*)c.tails, a.extremes = c.extremes;
     a.n_bins = c.counts ? c.n_bins : 1;
     for (int k = 0; k < K; ++k) {
-        a.lo[k] = c.counts ? c.lo[k] : 0.0, a.hi[k] = c.counts ? c.hi[k] : 1.0;
-        const double width = a.hi[k] - a.lo[k];
-        a.scale[k] = (double)a.n_bins / width;
+        const BinAxis ax = c.counts ? bin_axis(c.lo[k], c.hi[k], a.n_bins) : bin_axis(0.0, 1.0, a.n_bins);
+        a.lo[k] = ax.lo, a.hi[k] = ax.hi, a.scale[k] = ax.scale;
         a.thr[k] = c.tails ? c.threshold[k] : 0.0f;
     }
     const size_t lds_bytes = c.counts ? (size_t)K * (c.n_bins + 3) * sizeof(uint32_t) : 0;
-    const unsigned g = predictive_grid(c.n_rows, c.n_chains, pred_rows(D));
-    hipLaunchKernelGGL((predictive_kernel<D, YD>), dim3(g), dim3(PRED_LANES, PRED_WAVES), lds_bytes, s, a);
+    const unsigned g = predictive_grid(c.n_rows, c.n_chains, pred_rows(D), lds_bytes);
+    hipLaunchKernelGGL((predictive_kernel<D, YD>), dim3(g), dim3(HISTORY_LANES, HISTORY_WAVES), lds_bytes, s, a);
     return launch_status();
 }
 
