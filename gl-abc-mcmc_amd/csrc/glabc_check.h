@@ -314,15 +314,30 @@ inline int check_cross_moments(const float* history, int64_t n_rows, int32_t the
 
 // ---- glabc_abc_draws: the Model a fused rejection draw is compiled for and the range of draws, in the order include/glabc.h lists
 // the refusals.  The parameters' values are not looked at: a draw from a prior of scale 0 or NaN is what the arithmetic says it is
-inline int check_abc_model(const glabc_model* m)
+// the shapes the built-in simulators are compiled for, then the simulator's kind; theta_dim: what the caller's data has (a history's;
+// the Model's own where there is none), asked between the two
+inline int check_draw_sim(const glabc_model* m, int32_t theta_dim)
 {
     if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
     if (m->sim_kind == GLABC_SIM_GK && (m->theta_dim != 4 || m->y_dim != 8)) return GLABC_ERR_DIM;
     if (m->sim_kind == GLABC_SIM_ABS_GAUSS && m->y_dim != m->theta_dim) return GLABC_ERR_DIM;
+    if (theta_dim != m->theta_dim) return GLABC_ERR_DIM;
     if (m->sim_kind != GLABC_SIM_ABS_GAUSS && m->sim_kind != GLABC_SIM_GK) return GLABC_ERR_KIND;
+    return GLABC_OK;
+}
+
+// the priors a draw kernel draws theta from
+inline int check_draw_prior(const glabc_model* m)
+{
     if (m->prior.kind != GLABC_DIST_DIAG_GAUSS && m->prior.kind != GLABC_DIST_UNIFORM) return GLABC_ERR_KIND;
     if (m->prior.dim != m->theta_dim) return GLABC_ERR_KIND;
     return GLABC_OK;
+}
+
+inline int check_abc_model(const glabc_model* m)
+{
+    if (int e = check_draw_sim(m, m->theta_dim)) return e;
+    return check_draw_prior(m);
 }
 
 inline int check_abc_range(int64_t row0, const int64_t* ids, int64_t n, int64_t stride)
@@ -341,15 +356,7 @@ inline int check_abc_draws(const glabc_model* m, int64_t row0, const int64_t* id
 // ---- glabc_predictive_draws / glabc_predictive_counts: the Model a predictive draw is compiled for (check_abc_model's rules without
 // the prior, which is neither used nor examined), the history and the ids, in the order include/glabc.h lists the refusals; each
 // entry point adds what its own outputs ask
-inline int check_predictive_model(const glabc_model* m, int32_t theta_dim)
-{
-    if (m->theta_dim < 1 || m->theta_dim > GLABC_MAX_DIM || m->y_dim < 1 || m->y_dim > GLABC_MAX_DIM) return GLABC_ERR_DIM;
-    if (m->sim_kind == GLABC_SIM_GK && (m->theta_dim != 4 || m->y_dim != 8)) return GLABC_ERR_DIM;
-    if (m->sim_kind == GLABC_SIM_ABS_GAUSS && m->y_dim != m->theta_dim) return GLABC_ERR_DIM;
-    if (theta_dim != m->theta_dim) return GLABC_ERR_DIM;
-    if (m->sim_kind != GLABC_SIM_ABS_GAUSS && m->sim_kind != GLABC_SIM_GK) return GLABC_ERR_KIND;
-    return GLABC_OK;
-}
+inline int check_predictive_model(const glabc_model* m, int32_t theta_dim) { return check_draw_sim(m, theta_dim); }
 
 // the last id of a call, id0 + (n_rows - 1) * id_step + n_chains - 1, must be an int64
 inline int check_predictive_range(int64_t n_rows, int64_t n_chains, int64_t stride, int64_t id0, int64_t id_step)
@@ -409,15 +416,21 @@ inline int kde_check(const glabc_kde* k)
 
 // ---- glabc_smc_draws: check_abc_draws with a fifth output and the population between the Model and the range of draws, in the order
 // include/glabc.h lists the refusals.  The population's values are looked at (kde_check): a bandwidth of 0 has no mixture density
+// (the population's own rules, for glabc_rtc_smc_draws too)
+inline int check_draw_population(const glabc_kde* pop, int32_t theta_dim)
+{
+    if (int e = kde_check(pop)) return e;
+    if (!pop->cum_q) return GLABC_ERR_NULL;
+    return pop->dim != theta_dim ? GLABC_ERR_DIM : GLABC_OK;
+}
+
 inline int check_smc_draws(const glabc_model* m, const glabc_kde* pop, int64_t row0, const int64_t* ids, int64_t n, int64_t stride,
                            const float* theta_out, const float* y_out, const float* dis_out, const float* log_prior_out,
                            const uint8_t* accept_out)
 {
     if (!m || !pop || (!theta_out && !y_out && !dis_out && !log_prior_out && !accept_out)) return GLABC_ERR_NULL;
     if (int e = check_abc_model(m)) return e;
-    if (int e = kde_check(pop)) return e;
-    if (!pop->cum_q) return GLABC_ERR_NULL;
-    if (pop->dim != m->theta_dim) return GLABC_ERR_DIM;
+    if (int e = check_draw_population(pop, m->theta_dim)) return e;
     return check_abc_range(row0, ids, n, stride);
 }
 
@@ -482,8 +495,8 @@ inline int check_rtc_mix_run(const RtcShape& p, bool mix_program, const glabc_mo
 // ---- glabc_rtc_abc_draws / glabc_rtc_smc_draws: a launch of the run-time compiled DRAWS program of shape `p` -------------------------
 // draws_program: the program was built from the draws table (glabc_rtc_compile_draws, glabc_rtc_draws_kernels.h); no other program
 // holds a draw kernel.  any_output: one of the entry point's outputs is not NULL.  smc: glabc_rtc_smc_draws, which reads `pop` --
-// refused as glabc_smc_draws refuses it (kde_check, cum_q, the dimension), between the Model and the range of draws; the range is
-// check_abc_range's.  The order is the contract (include/glabc.h); the entry point has refused a NULL program before.
+// refused as glabc_smc_draws refuses it (check_draw_population), between the Model and the range of draws; the prior is
+// check_draw_prior's, the range check_abc_range's.  The order is the contract (include/glabc.h); the entry point has refused a NULL program before.
 inline int check_rtc_draws(const RtcShape& p, bool draws_program, const glabc_model* m, bool smc, const glabc_kde* pop, bool any_output,
                            int64_t row0, const int64_t* ids, int64_t n, int64_t stride)
 {
@@ -491,13 +504,9 @@ inline int check_rtc_draws(const RtcShape& p, bool draws_program, const glabc_mo
     if (m->sim_kind != GLABC_SIM_USER) return GLABC_ERR_KIND;
     if (!draws_program) return GLABC_ERR_KIND;
     if (m->theta_dim != p.theta_dim || m->y_dim != p.y_dim || m->noise.dim != p.noise_dim) return GLABC_ERR_DIM;
-    if (m->prior.kind != GLABC_DIST_DIAG_GAUSS && m->prior.kind != GLABC_DIST_UNIFORM) return GLABC_ERR_KIND;
-    if (m->prior.dim != m->theta_dim) return GLABC_ERR_KIND;
-    if (smc) {
-        if (int e = kde_check(pop)) return e;
-        if (!pop->cum_q) return GLABC_ERR_NULL;
-        if (pop->dim != m->theta_dim) return GLABC_ERR_DIM;
-    }
+    if (int e = check_draw_prior(m)) return e;
+    if (smc)
+        if (int e = check_draw_population(pop, m->theta_dim)) return e;
     return check_abc_range(row0, ids, n, stride);
 }
 

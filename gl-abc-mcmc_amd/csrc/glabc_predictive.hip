@@ -5,9 +5,9 @@
 // chain index; the walk over items of 64 chains x R rows (R = pred_rows(D): 16 / D rows, so about 16 loads are in flight per item),
 // the guarded loads, the uint32 table in LDS, the grid rule, the key and glabc_histogram's bin arithmetic are glabc_history.h's, which
 // argues what cannot be read, that a slot is inside the table and that no counter wraps.  An item loads the D row segments of its R
-// rows, all issued together; a lane outside the segment stores and counts nothing.  Then, per lane and row: the Philox blocks and
-// Box-Muller pairs of abc_draws_kernel under the predictive key, model_simulate and model_discrepancy_rows of glabc_device.h -- the
-// functions glabc_model_simulate / glabc_model_discrepancy inline, which is what makes the bits agree with their composition.
+// rows, all issued together; a lane outside the segment stores and counts nothing.  Then, per lane and row: the noise of a draw
+// (draw_noise of glabc_draw.h, what abc_draws_kernel calls) under the predictive key, model_simulate and model_discrepancy_rows
+// of glabc_device.h -- the functions glabc_model_simulate / glabc_model_discrepancy inline, which is what makes the bits agree with their composition.
 // Outputs.  Which are wanted is wave-uniform (a NULL pointer in the argument block), as in abc_draws_kernel:
 //   y, dis     plain stores in the history's layout (glabc_predictive_draws)
 //   counts     K = YD + 1 tables of n_bins + 3 uint32 counters in LDS (at most 9 x 1027 x 4 = 36 972 bytes: what a launch gets
@@ -27,9 +27,9 @@
 #include "glabc_check.h"
 #include "glabc_device.h"
 #include "glabc_dispatch.h"
+#include "glabc_draws_pack.h"
 #include "glabc_history.h"
 #include "glabc_launch.h"
-#include "glabc_pack.h"
 
 namespace glabc {
 
@@ -98,19 +98,10 @@ __global__ void __launch_bounds__(HISTORY_LANES* HISTORY_WAVES) predictive_kerne
             if (r < it.rows) {                                    // wave-uniform
                 const int64_t t = it.row0 + r;
                 const uint64_t id = (uint64_t)(a.id0 + t * a.id_step + c);
-                const uint32_t id_lo = (uint32_t)id, id_hi = (uint32_t)(id >> 32);
 
-                // y: glabc_model_simulate(eps = NULL) under the predictive key -- normal j is word pair (2j, 2j + 1) of the blocks (id, 0, b)
-                constexpr int ND = NoiseDim<YD>::value, NYB = (ND + 3) / 4;
-                float nrm[4 * NYB], eps[ND], theta[D], v[K];      // v: the statistics, y and then the distance
-#pragma unroll
-                for (int b = 0; b < NYB; ++b) {
-                    const glabc_u32x4 w = glabc_philox4x32_10(id_lo, id_hi, 0u, (uint32_t)b, a.key_lo, a.key_hi);
-                    glabc_normal_pair(w.v[0], w.v[1], &nrm[4 * b], &nrm[4 * b + 1]);
-                    glabc_normal_pair(w.v[2], w.v[3], &nrm[4 * b + 2], &nrm[4 * b + 3]);
-                }
-#pragma unroll
-                for (int j = 0; j < ND; ++j) eps[j] = nrm[j];
+                // y: glabc_model_simulate(eps = NULL) under the predictive key, the noise of a draw (glabc_draw.h)
+                float eps[NoiseDim<YD>::value], theta[D], v[K];   // v: the statistics, y and then the distance
+                draw_noise<YD>(id, a.key_lo, a.key_hi, eps);
 #pragma unroll
                 for (int j = 0; j < D; ++j) theta[j] = x[r][j];
                 {
@@ -221,16 +212,13 @@ template <int D, int YD>
 inline int launch_predictive(const PredCall& c, hipStream_t s)
 {
     constexpr int K = YD + 1;
-    glabc_chains none;
-    std::memset(&none, 0, sizeof none);
     PredArgs<D, YD> a;
     std::memset(&a, 0, sizeof a);
-    a.s = pack_args_rinv<D, YD>(c.model, nullptr, &c.model->prior, &none, nullptr, 0.0f);
+    a.s = pack_draw_model<D, YD>(c.model);
     a.hist = c.history;
     a.n_rows = c.n_rows, a.row_step = (int64_t)D * c.stride, a.n_chains = c.n_chains, a.stride = c.stride;
     a.id0 = c.id0, a.id_step = c.id_step;
-    const uint64_t key = c.seed ^ GLABC_PREDICTIVE_KEY;
-    a.key_lo = (uint32_t)key, a.key_hi = (uint32_t)(key >> 32);
+    split_key(c.seed ^ GLABC_PREDICTIVE_KEY, &a.key_lo, &a.key_hi);
     a.y = c.y, a.dis = c.dis, a.y_stride = c.y_stride, a.dis_stride = c.dis_stride;
     a.counts = (unsigned long long*)c.counts, a.tails = (unsigned long long*)c.tails, a.extremes = c.extremes;
     a.n_bins = c.counts ? c.n_bins : 1;

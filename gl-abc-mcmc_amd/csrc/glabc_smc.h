@@ -2,7 +2,8 @@
 // simulators (glabc_smc_draws) and as hiprtc instantiates it around a user's simulator (glabc_rtc_compile_draws, glabc_rtc_kernel.h).
 // include/glabc.h holds the specification of a draw.  No host includes: the header is handed to hiprtc as text.
 //
-// smc_draws_kernel<D, YD> is abc_draws_kernel (glabc_abc.h) with theta from a fitted population instead of the prior.  One lane owns
+// smc_draws_kernel<D, YD> is abc_draws_kernel (glabc_abc.h) with theta from a fitted population instead of the prior, the prior's
+// log-density as a fifth output and the distance +inf where that is -inf; the rest is glabc_draw.h's, which both call.  One lane owns
 // one draw and keeps it in registers from the ancestor to the distance: theta through kde_draw_row (glabc_kde_draw.h, what
 // glabc_kde_sample's kernel draws with), the prior's log-density through dist_log_prob, y through model_simulate and the distance
 // through model_discrepancy_rows of glabc_device.h -- the functions the row-wise entry points inline, which is what makes the bits
@@ -15,14 +16,11 @@
 // (profiles/smc_kernel_resources.txt).  Geometry: workgroups of 256 lanes, one draw per lane.
 #pragma once
 
-#include "glabc_abc.h"
 #include "glabc_device.h"
+#include "glabc_draw.h"
 #include "glabc_kde_draw.h"
 
 namespace glabc {
-
-constexpr int SMC_BLOCK = 256;
-constexpr int64_t SMC_MAX_LAUNCH = (int64_t)1 << 30;          // draws per launch: the grid stays far inside 32 bits
 
 template <int D, int YD>
 struct SmcArgs {
@@ -31,14 +29,8 @@ struct SmcArgs {
     const int64_t* cum_q;
     int64_t S;
     float bw[D];
-    const int64_t* ids;           // NULL: draw r has id row0 + r
-    int64_t row0, first, n, stride;                             // this launch covers draws first .. n - 1
-    uint32_t prop_lo, prop_hi, noise_lo, noise_hi, accept_lo, accept_hi;        // the three Philox keys
-    float* theta;
-    float* y;
-    float* dis;
+    DrawArgs d;                   // theta's key is the proposal's: the seed
     float* log_prior;
-    uint8_t* accept;
 };
 
 // The Model block of the kernel's argument, read where it is used.  The compiler loads a by-value argument in the entry block and sinks
@@ -60,60 +52,33 @@ GLABC_DEV const StepArgs<D, YD>& model_after_search(const SmcArgs<D, YD>& a)
 }
 
 template <int D, int YD>
-__global__ void __launch_bounds__(SMC_BLOCK) smc_draws_kernel(const SmcArgs<D, YD> a)
+__global__ void __launch_bounds__(DRAW_BLOCK) smc_draws_kernel(const SmcArgs<D, YD> a)
 {
-    const int64_t r = a.first + (int64_t)blockIdx.x * SMC_BLOCK + threadIdx.x;
-    if (r >= a.n) return;
-    const uint64_t id = (uint64_t)(a.ids ? a.ids[r] : a.row0 + r);
-    const uint32_t id_lo = (uint32_t)id, id_hi = (uint32_t)(id >> 32);
+    const int64_t r = draw_row(a.d);
+    if (r >= a.d.n) return;
+    const uint64_t id = draw_id(a.d, r);
 
     // theta: row id of glabc_kde_sample(population), through the function its kernel draws with (glabc_kde_draw.h)
-    float theta[D];
-    kde_draw_row<D>(a.x, a.cum_q, a.S, a.bw, id, a.prop_lo, a.prop_hi, theta);
-    if (a.theta) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) a.theta[(int64_t)j * a.stride + r] = theta[j];
-    }
-    if (!a.y && !a.dis && !a.log_prior && !a.accept) return;
+    float theta[D], y[YD];
+    kde_draw_row<D>(a.x, a.cum_q, a.S, a.bw, id, a.d.theta_lo, a.d.theta_hi, theta);
+    draw_store<D>(a.d.theta, a.d, r, theta);
+    if (!a.d.y && !a.d.dis && !a.log_prior && !a.d.accept) return;
     const StepArgs<D, YD>& m = model_after_search(a);
 
     // the prior's log-density: glabc_model_prior_log_prob; the distance and the acceptance need to know where it is -inf
     float lp = 0.0f;
-    if (a.dis || a.log_prior || a.accept) {
+    if (a.d.dis || a.log_prior || a.d.accept) {
         lp = dist_log_prob<D>(m.prior, theta);
         if (a.log_prior) a.log_prior[r] = lp;
     }
-    if (!a.y && !a.dis && !a.accept) return;
+    if (!a.d.y && !a.d.dis && !a.d.accept) return;
 
-    // y: glabc_model_simulate(eps = NULL) under the noise key, as in abc_draws_kernel
-    constexpr int ND = NoiseDim<YD>::value, NYB = (ND + 3) / 4;
-    float nrm[4 * NYB], eps[ND], y[YD];
-#pragma unroll
-    for (int b = 0; b < NYB; ++b) {
-        const glabc_u32x4 w = glabc_philox4x32_10(id_lo, id_hi, 0u, (uint32_t)b, a.noise_lo, a.noise_hi);
-        glabc_normal_pair(w.v[0], w.v[1], &nrm[4 * b], &nrm[4 * b + 1]);
-        glabc_normal_pair(w.v[2], w.v[3], &nrm[4 * b + 2], &nrm[4 * b + 3]);
-    }
-#pragma unroll
-    for (int j = 0; j < ND; ++j) eps[j] = nrm[j];
-    model_simulate<D, YD>(m, theta, eps, y);
-    if (a.y) {
-#pragma unroll
-        for (int j = 0; j < YD; ++j) a.y[(int64_t)j * a.stride + r] = y[j];
-    }
-    if (!a.dis && !a.accept) return;
+    draw_simulate<D, YD>(m, a.d, r, id, theta, y);
+    if (!a.d.dis && !a.d.accept) return;
 
     // outside the prior's support the distance is +inf: a select, so y above is still the simulated row
     const float d0 = model_discrepancy_rows<YD>(y, m.y_obs);
-    const float dis = lp == -__builtin_inff() ? __builtin_inff() : d0;
-    if (a.dis) a.dis[r] = dis;
-    if (!a.accept) return;
-
-    // the Model's own kernel relative to its mode, K(dis) / K(0), as in abc_draws_kernel
-    const glabc_u32x4 w = glabc_philox4x32_10(id_lo, id_hi, 0u, 0u, a.accept_lo, a.accept_hi);
-    const float u = glabc_uniform_f32(w.v[0]);
-    const float p = draw_accept_probability<D, YD>(m, dis);
-    a.accept[r] = u < p ? (uint8_t)1 : (uint8_t)0;              // a NaN distance: p is NaN, the comparison false; +inf: p is 0
+    draw_finish<D, YD>(m, a.d, r, id, lp == -__builtin_inff() ? __builtin_inff() : d0);
 }
 
 }  // namespace glabc

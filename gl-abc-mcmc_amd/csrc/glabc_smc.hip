@@ -1,7 +1,7 @@
 // glabc_smc.hip -- ABC-SMC proposals: glabc_smc_draws of include/glabc.h, which holds the specification of a draw.
 //
 // The kernel, smc_draws_kernel<D, YD>, lives in glabc_smc.h (a run-time compiled draws program instantiates it too, glabc_rtc.hip);
-// this file holds its nine built-in instantiations -- |theta| + noise at theta_dim 1 .. 8 and g-and-k --, the launcher and the entry point.
+// this file holds its nine built-in instantiations -- |theta| + noise at theta_dim 1 .. 8 and g-and-k -- and the entry point.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -9,25 +9,7 @@
 #include "glabc_check.h"
 #include "glabc_dispatch.h"
 #include "glabc_draws_pack.h"
-#include "glabc_launch.h"
 #include "glabc_smc.h"
-
-namespace glabc {
-
-template <int D, int YD>
-inline int launch_smc(const glabc_model* m, const glabc_kde* k, uint64_t seed, int64_t row0, const int64_t* ids, int64_t n,
-                      int64_t stride, float* theta, float* y, float* dis, float* log_prior, uint8_t* accept, hipStream_t s)
-{
-    SmcArgs<D, YD> a = pack_smc_args<D, YD>(m, k, seed, row0, ids, n, stride, theta, y, dis, log_prior, accept);
-    for (a.first = 0; a.first < n; a.first += SMC_MAX_LAUNCH) {
-        const int64_t part = n - a.first < SMC_MAX_LAUNCH ? n - a.first : SMC_MAX_LAUNCH;
-        hipLaunchKernelGGL((smc_draws_kernel<D, YD>), dim3(grid_for(part, SMC_BLOCK)), dim3(SMC_BLOCK), 0, s, a);
-        if (int e = launch_status()) return e;
-    }
-    return GLABC_OK;
-}
-
-}  // namespace glabc
 
 using namespace glabc;
 
@@ -40,12 +22,12 @@ __attribute__((visibility("default"))) int glabc_smc_draws(const glabc_model* mo
 {
     if (int e = check_smc_draws(model, population, row0, ids, n, stride, theta_out, y_out, dis_out, log_prior_out, accept_out)) return e;
     if (n == 0) return GLABC_OK;
+    const DrawsCall c{model, population, seed, row0, ids, n, stride, theta_out, y_out, dis_out, log_prior_out, accept_out};
     hipStream_t s = (hipStream_t)stream;
-    if (model->sim_kind == GLABC_SIM_GK)
-        return launch_smc<4, 8>(model, population, seed, row0, ids, n, stride, theta_out, y_out, dis_out, log_prior_out, accept_out, s);
+    if (model->sim_kind == GLABC_SIM_GK) return launch_builtin_draws(smc_draws_kernel<4, 8>, pack_smc_args<4, 8>(c), s);
     return dispatch_range<1, 8>(model->theta_dim, GLABC_ERR_DIM, [&](auto d) {
         constexpr int D = decltype(d)::value;
-        return launch_smc<D, D>(model, population, seed, row0, ids, n, stride, theta_out, y_out, dis_out, log_prior_out, accept_out, s);
+        return launch_builtin_draws(smc_draws_kernel<D, D>, pack_smc_args<D, D>(c), s);
     });
 }
 

@@ -150,18 +150,17 @@ def _path(ABCset, path, epsilon):
 
 
 # ---------------------------------------------------------------------------------- the fused path
+def _outputs(desc, n, dev, want):
+    """-> the dimension-major buffers {name: tensor} of the wanted outputs of a draws entry point (`desc`: the _Entry of the Model), and
+    ptr(name): the pointer the entry point takes for an output, None where it is not wanted or there is nothing to draw"""
+    shapes = {"theta": (desc.theta_dim, n), "y": (desc.y_dim, n)}
+    out = {name: torch.empty(shapes.get(name, (n,)), dtype=torch.uint8 if name == "accept" else torch.float32, device=dev) for name in want}
+    return out, lambda name: out[name].data_ptr() if name in out and n else None
+
+
 def _launch(desc, seed, row0, ids, n, dev, want):
     """glabc_abc_draws (`desc`: the _Entry of the Model) -> the dimension-major buffers {name: tensor} of the wanted outputs"""
-    out = {}
-    if "theta" in want:
-        out["theta"] = torch.empty(desc.theta_dim, n, dtype=torch.float32, device=dev)
-    if "y" in want:
-        out["y"] = torch.empty(desc.y_dim, n, dtype=torch.float32, device=dev)
-    if "distance" in want:
-        out["distance"] = torch.empty(n, dtype=torch.float32, device=dev)
-    if "accept" in want:
-        out["accept"] = torch.empty(n, dtype=torch.uint8, device=dev)
-    ptr = lambda name: out[name].data_ptr() if name in out and n else None          # noqa: E731
+    out, ptr = _outputs(desc, n, dev, want)
     if n:
         with torch.cuda.device(dev):
             desc.abc(seed, row0, None if ids is None else ids.data_ptr(), n, n, ptr("theta"), ptr("y"), ptr("distance"), ptr("accept"),
@@ -169,18 +168,17 @@ def _launch(desc, seed, row0, ids, n, dev, want):
     return out
 
 
-def draws(ABCset, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, device=None):
-    """``glabc_abc_draws`` (a ``CompiledModel``: ``glabc_rtc_abc_draws``) on device tensors -> Draws(theta (n, D), y (n, YD),
-    distance (n,), accept (n,) uint8), None for what `want` leaves out; theta and y are views of the kernel's dimension-major buffers.  Draw r has id ``ids[r]`` (any integers
-    in 0 .. 2^63 - 1, any order, repeats allowed; `n` must be their number) or ``row0 + r``; a draw depends on (Model, seed, id) only."""
+def _draw_arguments(outputs, n, row0, ids, want, seed, entry):
+    """What draws() here and in smc checks of its arguments -> (n, row0, want as a tuple, ids as a tensor or None, entry()).  `entry`
+    resolves and checks the Model (and the population), between the scalars and the ids, where its refusals have always come"""
     n = _count("n", n, 0)
     row0 = _count("row0", row0, 0)
     want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in OUTPUTS for w in want):
-        raise ValueError("want names one or more of %r, got %r" % (OUTPUTS, want))
+    if not want or any(w not in outputs for w in want):
+        raise ValueError("want names one or more of %r, got %r" % (outputs, want))
     if seed is None or isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("seed must be an integer, got %r" % (seed,))
-    desc = _fused_entry(ABCset, _epsilon(ABCset, epsilon, True), "glabc_abc_draws")
+    desc = entry()
     if ids is not None:
         if row0 != 0:
             raise ValueError("row0 must be 0 when ids are given, got %r" % (row0,))
@@ -189,9 +187,17 @@ def draws(ABCset, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, devi
             raise ValueError("ids are n = %d integers, got shape %r of %s" % (n, tuple(ids.shape), ids.dtype))
         if n and int(ids.min()) < 0:
             raise ValueError("ids must be >= 0, got %d" % int(ids.min()))
+    return n, row0, want, ids, desc
+
+
+def draws(ABCset, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilon=None, device=None):
+    """``glabc_abc_draws`` (a ``CompiledModel``: ``glabc_rtc_abc_draws``) on device tensors -> Draws(theta (n, D), y (n, YD),
+    distance (n,), accept (n,) uint8), None for what `want` leaves out; theta and y are views of the kernel's dimension-major buffers.  Draw r has id ``ids[r]`` (any integers
+    in 0 .. 2^63 - 1, any order, repeats allowed; `n` must be their number) or ``row0 + r``; a draw depends on (Model, seed, id) only."""
+    n, row0, want, ids, desc = _draw_arguments(OUTPUTS, n, row0, ids, want, seed,
+                                               lambda: _fused_entry(ABCset, _epsilon(ABCset, epsilon, True), "glabc_abc_draws"))
     dev = engine.require_device(device)
-    if ids is not None:
-        ids = ids.to(device=dev, dtype=torch.int64).contiguous()
+    ids = ids if ids is None else ids.to(device=dev, dtype=torch.int64).contiguous()
     out = _launch(desc, engine.draw_seed(seed), row0, ids, n, dev, want)
     return Draws(out["theta"].t() if "theta" in out else None, out["y"].t() if "y" in out else None, out.get("distance"), out.get("accept"))
 

@@ -52,9 +52,7 @@ Draws = namedtuple("Draws", "theta y distance log_prior accept")
 # ---------------------------------------------------------------------------------- glabc_smc_draws
 def _launch(desc, kde, seed, row0, ids, n, dev, want):
     """glabc_smc_draws (`desc`: the rejection._Entry of the Model) -> the dimension-major buffers {name: tensor} of the wanted outputs"""
-    shapes = {"theta": (desc.theta_dim, n), "y": (desc.y_dim, n), "distance": (n,), "log_prior": (n,), "accept": (n,)}
-    out = {name: torch.empty(shapes[name], dtype=torch.uint8 if name == "accept" else torch.float32, device=dev) for name in want}
-    ptr = lambda name: out[name].data_ptr() if name in out and n else None          # noqa: E731
+    out, ptr = rejection._outputs(desc, n, dev, want)
     if n:
         with torch.cuda.device(dev):
             desc.smc(kde.descriptor(), seed, row0, None if ids is None else ids.data_ptr(), n, n, ptr("theta"), ptr("y"), ptr("distance"),
@@ -68,31 +66,19 @@ def draws(ABCset, population, n, *, seed, row0=0, ids=None, want=OUTPUTS, epsilo
     ``KernelDensity`` of theta_dim features.  Draw r has id ``ids[r]`` (any integers in 0 .. 2^63 - 1, any order, repeats allowed;
     `n` must be their number) or ``row0 + r``; a draw depends on (Model, population, seed, id) only.  The distance of a proposal
     of prior density 0 is +inf."""
-    n = rejection._count("n", n, 0)
-    row0 = rejection._count("row0", row0, 0)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in OUTPUTS for w in want):
-        raise ValueError("want names one or more of %r, got %r" % (OUTPUTS, want))
-    if seed is None or isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-        raise ValueError("seed must be an integer, got %r" % (seed,))
-    desc = rejection._fused_entry(ABCset, rejection._epsilon(ABCset, epsilon, True), "glabc_smc_draws")
-    if not isinstance(population, KernelDensity) or not population._fitted:
-        raise ValueError("population must be a fitted KernelDensity, got %r" % (population,))
-    if population.dim != desc.theta_dim:
-        raise ValueError("population has %d features, the Model %d parameters" % (population.dim, desc.theta_dim))
-    if ids is not None:
-        if row0 != 0:
-            raise ValueError("row0 must be 0 when ids are given, got %r" % (row0,))
-        ids = torch.as_tensor(ids)
-        if ids.dim() != 1 or ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.numel() != n:
-            raise ValueError("ids are n = %d integers, got shape %r of %s" % (n, tuple(ids.shape), ids.dtype))
-        if n and int(ids.min()) < 0:
-            raise ValueError("ids must be >= 0, got %d" % int(ids.min()))
+    def entry():
+        desc = rejection._fused_entry(ABCset, rejection._epsilon(ABCset, epsilon, True), "glabc_smc_draws")
+        if not isinstance(population, KernelDensity) or not population._fitted:
+            raise ValueError("population must be a fitted KernelDensity, got %r" % (population,))
+        if population.dim != desc.theta_dim:
+            raise ValueError("population has %d features, the Model %d parameters" % (population.dim, desc.theta_dim))
+        return desc
+
+    n, row0, want, ids, desc = rejection._draw_arguments(OUTPUTS, n, row0, ids, want, seed, entry)
     dev = engine.require_device(device)
     if population.device != dev:
         raise ValueError("population lives on %s, the draws on %s" % (population.device, dev))
-    if ids is not None:
-        ids = ids.to(device=dev, dtype=torch.int64).contiguous()
+    ids = ids if ids is None else ids.to(device=dev, dtype=torch.int64).contiguous()
     out = _launch(desc, population, engine.draw_seed(seed), row0, ids, n, dev, want)
     return Draws(out["theta"].t() if "theta" in out else None, out["y"].t() if "y" in out else None, out.get("distance"),
                  out.get("log_prior"), out.get("accept"))

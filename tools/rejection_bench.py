@@ -81,7 +81,7 @@ def main():
     desc = model.descriptor()
     n = a.draws
     out_b = torch.empty(n, dtype=torch.float32, device=dev)
-    fused = lambda: rejection._sweep(desc, SEED, n, dev, "distance")          # noqa: E731
+    fused = lambda: rejection._sweep(rejection._Entry(desc), SEED, n, dev, "distance")          # noqa: E731
     twin = lambda: composed(desc, n, dev, out_b)                               # noqa: E731
     for _ in range(a.warmup):
         fused()

@@ -77,7 +77,7 @@ def sweep(model, S, n, dev, a):
     desc = model.descriptor()
     r = rejection.sample(model, 64 * S, kernel="hard", n_accept=S, seed=SEED)
     kde = smc.KernelDensity("silverman", device=dev).fit(r.theta)
-    fused = lambda: smc._launch(desc, kde, SEED, 0, None, n, dev, ("distance",))["distance"]          # noqa: E731
+    fused = lambda: smc._launch(rejection._Entry(desc), kde, SEED, 0, None, n, dev, ("distance",))["distance"]          # noqa: E731
     twin = lambda: composed(desc, kde, n, dev)                                                        # noqa: E731
     for _ in range(a.warmup):
         fused()
