@@ -370,12 +370,24 @@ inline int check_predictive_range(int64_t n_rows, int64_t n_chains, int64_t stri
     return GLABC_OK;
 }
 
+// The Model of a predictive call, asked between the pointers and the numbers.  The built-in entry points: check_predictive_model.  The
+// launch of a run-time compiled predictive program has examined the Model against its program before (check_rtc_predictive_program):
+// what is left is the history's theta_dim.  The prior is neither used nor examined by either.
+struct PredModelCheck {
+    bool rtc = false;
+    int operator()(const glabc_model* m, int32_t theta_dim) const
+    {
+        if (!rtc) return check_predictive_model(m, theta_dim);
+        return theta_dim != m->theta_dim ? GLABC_ERR_DIM : GLABC_OK;
+    }
+};
+
 inline int check_predictive_draws(const glabc_model* m, const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains,
                                   int64_t stride, int64_t id0, int64_t id_step, const float* y_out, int64_t y_stride, const float* dis_out,
-                                  int64_t dis_stride)
+                                  int64_t dis_stride, const PredModelCheck& model_check = PredModelCheck())
 {
     if (!m || !history || (!y_out && !dis_out)) return GLABC_ERR_NULL;
-    if (int e = check_predictive_model(m, theta_dim)) return e;
+    if (int e = model_check(m, theta_dim)) return e;
     if (n_rows < 1 || n_chains < 0 || stride < n_chains) return GLABC_ERR_ARG;
     if ((y_out && y_stride < n_chains) || (dis_out && dis_stride < n_chains)) return GLABC_ERR_ARG;
     return check_predictive_range(n_rows, n_chains, stride, id0, id_step);
@@ -383,11 +395,12 @@ inline int check_predictive_draws(const glabc_model* m, const float* history, in
 
 inline int check_predictive_counts(const glabc_model* m, const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains,
                                    int64_t stride, int64_t id0, int64_t id_step, int32_t n_bins, const double* lo, const double* hi,
-                                   const float* threshold, const uint64_t* counts, const uint64_t* tails, const uint32_t* extremes)
+                                   const float* threshold, const uint64_t* counts, const uint64_t* tails, const uint32_t* extremes,
+                                   const PredModelCheck& model_check = PredModelCheck())
 {
     if (!m || !history || (!counts && !tails && !extremes)) return GLABC_ERR_NULL;
     if ((counts && (!lo || !hi)) || (tails && !threshold)) return GLABC_ERR_NULL;
-    if (int e = check_predictive_model(m, theta_dim)) return e;
+    if (int e = model_check(m, theta_dim)) return e;
     if (int e = check_predictive_range(n_rows, n_chains, stride, id0, id_step)) return e;
     const int n_stats = m->y_dim + 1;
     if (counts) {
@@ -508,6 +521,20 @@ inline int check_rtc_draws(const RtcShape& p, bool draws_program, const glabc_mo
     if (smc)
         if (int e = check_draw_population(pop, m->theta_dim)) return e;
     return check_abc_range(row0, ids, n, stride);
+}
+
+// ---- glabc_rtc_predictive_draws / glabc_rtc_predictive_counts: a launch of the run-time compiled PREDICTIVE program of shape `p` -------
+// pred_program: the program was built from the predictive table (glabc_rtc_compile_predictive, glabc_rtc_predictive_kernels.h); no
+// other program holds predictive_kernel.  The entry point has refused a NULL program before; after this, check_predictive_draws /
+// check_predictive_counts with PredModelCheck{true} refuse what the built-in entry points refuse, in their order.  The prior is not
+// looked at: theta comes from the history.  The order is the contract (include/glabc.h).
+inline int check_rtc_predictive_program(const RtcShape& p, bool pred_program, const glabc_model* m)
+{
+    if (!m) return GLABC_ERR_NULL;
+    if (m->sim_kind != GLABC_SIM_USER) return GLABC_ERR_KIND;
+    if (!pred_program) return GLABC_ERR_KIND;
+    if (m->theta_dim != p.theta_dim || m->y_dim != p.y_dim || m->noise.dim != p.noise_dim) return GLABC_ERR_DIM;
+    return GLABC_OK;
 }
 
 }  // namespace glabc

@@ -1,12 +1,15 @@
 // glabc_history.h -- what the kernels that walk a chain-major history share: the guarded row-segment load (glabc_diag.hip,
 // glabc_quant.hip, glabc_joint.hip, glabc_predictive.hip) and, for the three that count into a uint32 table in LDS, the order-preserving
 // key, glabc_histogram's bin arithmetic, the walk over items of 64 chains x ROWS rows, the table's zeroing and flush, and the grid
-// rule.  Host and device; never handed to hiprtc.  The counting kernels' three safety arguments are made here, once: nothing behind a
-// segment's bytes can be read (load_segment, Item), a slot is below the table's size (bin_inside, lds_add), no counter wraps (history_grid).
+// rule.  Host and device, and handed to hiprtc as text with glabc_predictive.h (a run-time compiled predictive program).  The counting
+// kernels' three safety arguments are made here, once: nothing behind a segment's bytes can be read (load_segment, Item), a slot is
+// below the table's size (bin_inside, lds_add), no counter wraps (history_grid).
 #pragma once
+#if !defined(__HIPCC_RTC__)          // hiprtc (glabc_rtc.hip) brings the HIP device declarations and the fixed-width types itself
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#endif
 
 namespace glabc {
 

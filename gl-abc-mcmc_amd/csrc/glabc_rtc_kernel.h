@@ -27,13 +27,21 @@
 // GLABC_RTC_DRAWS (glabc_rtc_compile_draws) instantiates no sampler at all: abc_draws_kernel (glabc_abc.h) and smc_draws_kernel
 // (glabc_smc.h), the templates glabc_abc_draws and glabc_smc_draws are instantiated from, with the user's function where the built-in
 // simulators are.  GLABC_RTC_ALGO / _N / _L are not defined for such a program.
+//
+// GLABC_RTC_PREDICTIVE (glabc_rtc_compile_predictive) instantiates predictive_kernel (glabc_predictive.h), the template
+// glabc_predictive_draws and glabc_predictive_counts are instantiated from, at GLABC_RTC_PRED_ROWS rows per item, and nothing else.
 #pragma once
 
 #include "glabc_sampler.h"
 
 namespace glabc {
 
-#if defined(GLABC_RTC_DRAWS)
+#if defined(GLABC_RTC_PREDICTIVE)
+}  // namespace glabc
+#include "glabc_predictive.h"
+namespace glabc {
+template __global__ void predictive_kernel<GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_PRED_ROWS>(const PredArgs<GLABC_RTC_D, GLABC_RTC_YD>);
+#elif defined(GLABC_RTC_DRAWS)
 }  // namespace glabc
 #include "glabc_abc.h"
 #include "glabc_smc.h"

@@ -39,6 +39,7 @@ FLAG_LW64 = 4
 FLAG_HAS_GRAD = 8
 
 OK = 0
+ERR_ARG = -4                   # include/glabc.h GLABC_ERR_ARG: of a run-time compile, a source that does not compile
 
 _f8 = C.c_float * MAX_DIM
 
@@ -345,6 +346,12 @@ ENTRY_POINTS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_rtc_smc_draws": (C.c_int, [C.c_void_p, _P(Model), _P(Kde), C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glabc_rtc_compile_predictive": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),
+    "glabc_rtc_predictive_draws": (C.c_int, [C.c_void_p, _P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint64,
+                                             C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "glabc_rtc_predictive_counts": (C.c_int, [C.c_void_p, _P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint64,
+                                              C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "glabc_selftest_numerics": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "glabc_selftest_sqrt": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "glabc_selftest_rowsum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -54,6 +54,11 @@ kernel in it) and checks them, bit for bit, against the composition of entry poi
 it is handed out.  A user prior (``GLABC_USER_PRIOR``) and a Gamma prior have no draws program: theta is drawn from a DiagGaussian
 or Uniform descriptor prior there.
 
+``predictive`` runs fused on a ``CompiledModel`` too: ``predictive_program()`` compiles ``predictive_kernel`` of
+``glabc_predictive_counts`` / ``glabc_predictive_draws`` around the source (``glabc_rtc_compile_predictive``; a program of its own in the
+cache) and checks it, bit for bit, against the composition of entry points that specifies a predictive draw before it is handed
+out.  Any prior will do, a user prior included: theta comes from the history.
+
 Use + - * / fmaf sqrtf fabsf and the ``glabc_*`` functions of include/glabc_numerics.h (``glabc_expf``,
 ``glabc_logf``, ``glabc_sincos2pi`` ...) for results that a CPU build of the same source reproduces bit for bit.
 """
@@ -88,6 +93,8 @@ class CompiledModel:
         self._programs = {}
         self._checked = set()
         self._failed = {}                                 # (algorithm, batch size) -> message of the failed self-check
+        self._predictive_rows = 1                         # rows per item the predictive program was compiled with
+        self._uncompiled = {}                             # the predictive program's key -> message of the compile that failed
         self.user_prior, self.user_discrepancy, self.user_kernel = (self._announces(m) for m in
                                                                     ("GLABC_USER_PRIOR", "GLABC_USER_DISCREPANCY", "GLABC_USER_KERNEL"))
 
@@ -406,6 +413,187 @@ class CompiledModel:
                 alone = fused(pop, (k,))[k]
                 if not np.array_equal(alone.view(np.uint8), got[k].view(np.uint8)):
                     refuse(kernel, k, " asked for alone")
+        return True
+
+    # ---- the predictive program: predictive_kernel around the source (predictive.py) -----------------------------------------
+    PREDICTIVE = "predictive"
+
+    @staticmethod
+    def predictive_rows():
+        """rows per item of a predictive program compiled now: csrc/glabc_rtc_predictive_kernels.h rtc_predictive_rows restated
+        (RTC_PRED_ROWS = 1; GLABC_RTC_PRED_ROWS=1..16 in the environment forces another, any other value is ignored)"""
+        try:
+            rows = int(os.environ.get("GLABC_RTC_PRED_ROWS", "1"))
+        except ValueError:
+            return 1
+        return rows if 1 <= rows <= 16 else 1
+
+    def predictive_program(self):
+        """The handle of the predictive program (glabc_rtc_compile_predictive), compiled once and self-checked
+        (self_check_predictive) before it is handed out; a failed check raises SimulatorSelfCheckError, releases the program and is
+        remembered.  Any prior will do: theta comes from the history."""
+        key = (self.PREDICTIVE,)
+        if key in self._failed:
+            raise SimulatorSelfCheckError(self._failed[key])
+        if key in self._uncompiled:                      # a source that did not compile is not handed to hiprtc again
+            raise SimulatorCompileError(self._uncompiled[key])
+        if key not in self._programs:
+            handle = C.c_void_p()
+            log = C.create_string_buffer(1 << 16)
+            rows = self.predictive_rows()
+            rc = _capi.lib().glabc_rtc_compile_predictive(self.simulator_source.encode(), self.theta_dim, self.y_dim, self.noise_dim,
+                                                          C.byref(handle), log, len(log))
+            if rc != _capi.OK:
+                message = "glabc_rtc_compile_predictive failed (status %d):\n%s" % (rc, log.value.decode(errors="replace"))
+                if rc == _capi.ERR_ARG:                  # the source's own defect; no device (GLABC_ERR_NO_DEVICE) may be there next time
+                    self._uncompiled[key] = message
+                raise SimulatorCompileError(message)
+            self._programs[key] = handle
+            self._predictive_rows = rows
+        if key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
+            try:
+                self.self_check_predictive(self._programs[key], rows=self._predictive_rows)
+                self._checked.add(key)
+            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
+                handle = self._programs.pop(key, None)
+                if handle is not None:
+                    _capi.lib().glabc_rtc_release(handle)
+                if isinstance(exc, SimulatorSelfCheckError):
+                    self._failed[key] = str(exc)
+                raise
+        return self._programs[key]
+
+    def composed_predictive(self, handle, desc, hist, seed, id0, id_step):
+        """The predictive draws of the chain-major device history `hist` (T, D, C) as include/glabc.h specifies them, from the entry
+        points a draw is composed of: per row t, eps from glabc_dist_forward of a standard DiagGaussian under seed ^
+        GLABC_PREDICTIVE_KEY at row0 = id0 + t id_step, y from glabc_rtc_simulate, the distance from glabc_rtc_model_rows /
+        glabc_model_discrepancy -> (y (T, YD, C), distance (T, C)) device tensors"""
+        from .predictive import PREDICTIVE_KEY
+        lib, dev = _capi.lib(), hist.device
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        n_rows, _, n = hist.shape
+        key = (seed ^ PREDICTIVE_KEY) & 0xFFFFFFFFFFFFFFFF
+        ys, ds = [], []
+        with torch.cuda.device(dev):
+            for t in range(n_rows):
+                theta = hist[t].t().contiguous()
+                e = torch.empty(self.noise_dim, n, dtype=torch.float32, device=dev)
+                lq = torch.empty(n, dtype=torch.float32, device=dev)
+                _capi.check(lib.glabc_dist_forward(C.byref(desc.noise), n, key, id0 + t * id_step, e.data_ptr(), lq.data_ptr(), stream),
+                            "glabc_dist_forward")
+                eps = e.t().contiguous()
+                y = torch.empty(n, self.y_dim, dtype=torch.float32, device=dev)
+                _capi.check(lib.glabc_rtc_simulate(handle, theta.data_ptr(), eps.data_ptr(), n, y.data_ptr(), stream), "glabc_rtc_simulate")
+                dis = torch.empty(n, dtype=torch.float32, device=dev)
+                if self.user_discrepancy:
+                    _capi.check(lib.glabc_rtc_model_rows(handle, C.byref(desc), _capi.RTC_DISCREPANCY, y.data_ptr(), n, dis.data_ptr(), stream),
+                                "glabc_rtc_model_rows")
+                else:
+                    _capi.check(lib.glabc_model_discrepancy(C.byref(desc), y.data_ptr(), n, dis.data_ptr(), stream), "glabc_model_discrepancy")
+                ys.append(y.t())
+                ds.append(dis)
+        return torch.stack(ys).contiguous(), torch.stack(ds).contiguous()
+
+    def self_check_predictive(self, handle, seed=20240229, rows=None):
+        """predictive_kernel of a freshly compiled predictive program against the composition that specifies a draw
+        (composed_predictive), bit for bit (a NaN matching a NaN): 65 chains x 2 R + 1 rows (R the kernel's rows per item: a partial
+        segment and a partial item), a stride that is no multiple of 4, ids that cross 2^32 inside the call and a second run past 2^40
+        with id_step > n_chains; theta about 1 with a spread of 0.5 in every coordinate, whatever the prior, which is never evaluated;
+        y and the distance together, then each alone; counts, tails and extremes -- together, then each table
+        alone -- against the same bin arithmetic (predictive._torch_tables, glabc_key_counts' key) on the composed draws, as equal
+        integers.  Runs once per Model (a few ms); GLABC_RTC_SELF_CHECK=0 skips it."""
+        from . import predictive
+        lib, dev = _capi.lib(), engine.require_device(None)
+        desc = self.descriptor()
+        d, yd, k = self.theta_dim, self.y_dim, self.y_dim + 1
+        rows = self.predictive_rows() if rows is None else int(rows)
+        n, n_rows, stride = 65, 2 * rows + 1, 65 + 17
+        g = torch.Generator().manual_seed(seed)
+        theta = (1.0 + 0.5 * torch.randn(n_rows, d, n, generator=g, dtype=torch.float64)).to(torch.float32)
+        buf = torch.full((n_rows, d, stride), float("nan"), dtype=torch.float32)
+        buf[:, :, :n] = theta
+        buf = buf.to(dev)
+        hist = buf[:, :, :n]
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+        def refuse(name, detail=""):
+            raise SimulatorSelfCheckError(
+                "the run-time compiled predictive_kernel disagrees with the composition of entry points that specifies a predictive draw "
+                "in `%s`%s: refusing to check with it (use path='generic', and please report the simulator source)" % (name, detail))
+
+        def same(a, b):
+            return bool(((a.view(torch.int32) == b.view(torch.int32)) | (torch.isnan(a) & torch.isnan(b))).all())
+
+        def draws(id0, id_step, want):
+            y = torch.empty(n_rows, yd, n + 3, dtype=torch.float32, device=dev) if "y" in want else None
+            dis = torch.empty(n_rows, n + 1, dtype=torch.float32, device=dev) if "distance" in want else None
+            with torch.cuda.device(dev):
+                _capi.check(lib.glabc_rtc_predictive_draws(handle, C.byref(desc), buf.data_ptr(), n_rows, d, n, stride, seed, id0, id_step,
+                                                           None if y is None else y.data_ptr(), n + 3, None if dis is None else dis.data_ptr(),
+                                                           n + 1, stream), "glabc_rtc_predictive_draws")
+            return (None if y is None else y[:, :, :n]), (None if dis is None else dis[:, :n])
+
+        def tables(id0, id_step, bins, lim, thr, want):
+            counts = torch.zeros(k, bins + 3, dtype=torch.int64, device=dev) if "counts" in want else None
+            tails = torch.zeros(k, 4, dtype=torch.int64, device=dev) if "tails" in want else None
+            extremes = (torch.from_numpy(np.array([predictive.KEY_NONE] * k, np.uint32).view(np.int32)).to(dev)
+                        if "extremes" in want else None)
+            lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+            ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+            with torch.cuda.device(dev):
+                _capi.check(lib.glabc_rtc_predictive_counts(
+                    handle, C.byref(desc), buf.data_ptr(), n_rows, d, n, stride, seed, id0, id_step, bins,
+                    lo.ctypes.data if counts is not None else None, hi.ctypes.data if counts is not None else None,
+                    thr.ctypes.data if tails is not None else None, ptr(counts), ptr(tails), ptr(extremes), stream),
+                    "glabc_rtc_predictive_counts")
+            out = {}
+            if counts is not None:
+                out["counts"] = counts.cpu().numpy().view(np.uint64)
+            if tails is not None:
+                out["tails"] = tails.cpu().numpy().view(np.uint64)
+            if extremes is not None:
+                out["extremes"] = extremes.cpu().numpy().view(np.uint32)
+            return out
+
+        for id0, id_step in ((2 ** 32 - 40, n), (2 ** 40 + 5, n + 7)):
+            where = " (id0 %d, id_step %d)" % (id0, id_step)
+            want_y, want_dis = self.composed_predictive(handle, desc, hist, seed, id0, id_step)
+            y, dis = draws(id0, id_step, ("y", "distance"))
+            if not same(y, want_y):
+                refuse("y", where)
+            if not same(dis, want_dis):
+                refuse("distance", where)
+            if not same(draws(id0, id_step, ("y",))[0], want_y):
+                refuse("y", " asked for alone" + where)
+            if not same(draws(id0, id_step, ("distance",))[1], want_dis):
+                refuse("distance", " asked for alone" + where)
+            # the tables of the composed draws: N x K statistics, the bins over a range with values on both sides, thresholds at a drawn value
+            stats = torch.cat([want_y.permute(0, 2, 1).reshape(-1, yd), want_dis.reshape(-1, 1)], dim=1)
+            host = stats.cpu().numpy()
+            lim, thr = np.empty((k, 2)), np.empty(k, np.float32)
+            for j in range(k):
+                v = np.sort(host[:, j][np.isfinite(host[:, j])])
+                if v.size == 0:
+                    lim[j], thr[j] = (0.0, 1.0), 0.0
+                else:
+                    lim[j], thr[j] = (float(v[v.size // 10]), float(v[9 * v.size // 10])), v[v.size // 2]
+                if not lim[j, 0] < lim[j, 1]:
+                    lim[j] = lim[j, 0] - 0.5, lim[j, 0] + 0.5
+            bins = 7
+            ref = dict(zip(("counts", "tails"), predictive._torch_tables(stats, bins, lim, thr)))
+            ref["extremes"] = np.array([predictive.KEY_NONE] * k, np.uint32)
+            for j in range(k):
+                v = host[:, j][~np.isnan(host[:, j])]
+                if v.size:                                             # include/glabc.h glabc_key_counts: -0 is +0, order-preserving
+                    u = np.where(v == 0, np.float32(0.0), v).astype(np.float32).view(np.uint32)
+                    keys = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+                    ref["extremes"][j] = keys.min(), keys.max()
+            got = tables(id0, id_step, bins, lim, thr, ("counts", "tails", "extremes"))
+            for name in ("counts", "tails", "extremes"):
+                if not np.array_equal(got[name], ref[name]):
+                    refuse(name, where)
+                if not np.array_equal(tables(id0, id_step, bins, lim, thr, (name,))[name], ref[name]):
+                    refuse(name, " asked for alone" + where)
         return True
 
     def _gamma_prior(self):

@@ -14,7 +14,17 @@ the tables are the same bits in every launch geometry and additive over shards o
 ``chain0`` / ``n_chains_total`` (and ``row0``), all-reduces the integer tables of ``terms`` and every rank reads ``summary`` of the
 very draws the whole job would have made.  There is no CPU implementation of this path.
 
-Generic path (``path="generic"``, and every Model the kernel does not take: callback Models, a ``CompiledModel``, CPU tensors).
+A ``CompiledModel`` takes the same path through a kernel of its own: ``CompiledModel.predictive_program()`` compiles
+``predictive_kernel`` around the user's simulator (``glabc_rtc_compile_predictive``; the user's distance where the source announces
+``GLABC_USER_DISCREPANCY``), checks it bit for bit against the composition of entry points that specifies a draw, and
+``glabc_rtc_predictive_counts`` / ``glabc_rtc_predictive_draws`` launch it: ``path="fused"`` on any CUDA history, ``path="auto"``
+when the history is a CUDA tensor.  So ``check(CompiledModel, cuda_history)`` under ``"auto"`` draws the same law from the Philox
+streams, not from torch's generator as it did when this route was the generic one: it is a function of (Model, theta, seed, id),
+and ``terms`` / ``combine`` with ``chain0``, ``n_chains_total`` and ``row0`` are exact for user Models too.  Under ``"auto"`` a source
+that does not compile or a program that fails its self-check warns (``RuntimeWarning``) and runs the generic path; under
+``"fused"`` it raises.
+
+Generic path (``path="generic"``, and every Model the kernels do not take: callback Models, CPU tensors).
 Plain torch: ``Model.generate_samples(theta, 1)`` in chunks of rows, ``Model.discrepancy`` where the Model has one (otherwise there
 are y_dim statistics and the distance fields are ``None``), and the same bin arithmetic in float64 torch.  The noise comes from
 torch's generator, seeded with ``seed`` inside ``torch.random.fork_rng`` (``seed=None``: the global generator as it stands); ids do
@@ -23,10 +33,10 @@ not apply.
 ``range=None`` takes two passes on the fused path -- extremes and tails, then the counts over the exact minimum and maximum, a
 constant statistic widened by +-0.5 as ``diagnostics.histogram`` widens it -- and an explicit ``(K, 2)`` range one.
 
-Out of scope: compiling a user's simulator into the kernel (the draw kernels' ``CompiledModel.draws_program`` was its own piece of
-work), test quantities other than the coordinates and the distance, and joint summaries of ``y_rep``.
+Out of scope: test quantities other than the coordinates and the distance, and joint summaries of ``y_rep``.
 """
 import ctypes as C
+import warnings
 from collections import namedtuple
 
 import numpy as np
@@ -112,19 +122,52 @@ def accepted(Model):
     return desc if rc == _capi.OK else None
 
 
+class Fused(namedtuple("Fused", "desc program")):
+    """What the fused path launches: the glabc_model, and the handle of the run-time compiled predictive program of a CompiledModel
+    (None: the built-in entry points)"""
+
+    def draws(self, *args):
+        if self.program is None:
+            _capi.check(_capi.lib().glabc_predictive_draws(C.byref(self.desc), *args), "glabc_predictive_draws")
+        else:
+            _capi.check(_capi.lib().glabc_rtc_predictive_draws(self.program, C.byref(self.desc), *args), "glabc_rtc_predictive_draws")
+
+    def counts(self, *args):
+        if self.program is None:
+            _capi.check(_capi.lib().glabc_predictive_counts(C.byref(self.desc), *args), "glabc_predictive_counts")
+        else:
+            _capi.check(_capi.lib().glabc_rtc_predictive_counts(self.program, C.byref(self.desc), *args), "glabc_rtc_predictive_counts")
+
+
 def _path(Model, history, path):
-    """The one place that decides what a call runs -> the glabc_model of the fused path, or None for the generic one"""
+    """The one place that decides what a call runs -> the Fused of the fused path, or None for the generic one"""
+    from .compiled import CompiledModel, SimulatorCompileError, SimulatorSelfCheckError
     if path not in ("auto", "fused", "generic"):
         raise ValueError('path is "auto", "fused" or "generic", got %r' % (path,))
     if path == "generic":
         return None
+    on_gpu = isinstance(history, torch.Tensor) and history.is_cuda
+    if isinstance(Model, CompiledModel):
+        # the program needs a device to be loaded on: "auto" asks for it only where the history lives on one
+        if path == "auto" and not (on_gpu and torch.cuda.is_available()):
+            return None
+        if path == "fused" and not on_gpu:
+            raise ValueError('path="fused" on a CompiledModel needs a history on the GPU: its predictive program is launched in place')
+        try:
+            return Fused(Model.descriptor(), Model.predictive_program())
+        except (SimulatorCompileError, SimulatorSelfCheckError) as exc:
+            if path == "fused":
+                raise
+            warnings.warn("the predictive program of this CompiledModel is not available (%s): running the generic path"
+                          % (str(exc).splitlines()[0],), RuntimeWarning, stacklevel=3)
+            return None
     desc = accepted(Model)
     if path == "fused":
         if desc is None:
             raise ValueError('path="fused" needs a Model whose descriptor() glabc_predictive_counts accepts (|theta| + noise or '
-                             "g-and-k), got %r" % (type(Model).__name__,))
-        return desc
-    return desc if isinstance(history, torch.Tensor) and history.is_cuda else None
+                             "g-and-k) or a CompiledModel, got %r" % (type(Model).__name__,))
+        return Fused(desc, None)
+    return Fused(desc, None) if desc is not None and on_gpu else None
 
 
 # ---------------------------------------------------------------------------------- the fused path
@@ -132,11 +175,11 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _fused_counts(desc, h, seed, id0, id_step, bins, lim, thr, want):
-    """one glabc_predictive_counts call on the chain-major rows `h` -> (counts [K][bins + 3], tails [K][4], extremes [K][2]) as
-    NumPy arrays, None for what `want` leaves out"""
+def _fused_counts(fused, h, seed, id0, id_step, bins, lim, thr, want):
+    """one glabc_predictive_counts / glabc_rtc_predictive_counts call on the chain-major rows `h` -> (counts [K][bins + 3], tails [K][4],
+    extremes [K][2]) as NumPy arrays, None for what `want` leaves out"""
     n_rows, d, stride = h.shape
-    k = desc.y_dim + 1
+    k = fused.desc.y_dim + 1
     dev = h.device
     counts = torch.zeros(k, bins + 3, dtype=torch.int64, device=dev) if "counts" in want else None
     tails = torch.zeros(k, 4, dtype=torch.int64, device=dev) if "tails" in want else None
@@ -146,10 +189,9 @@ def _fused_counts(desc, h, seed, id0, id_step, bins, lim, thr, want):
         lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
     ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().glabc_predictive_counts(
-            C.byref(desc), h.data_ptr(), n_rows, d, stride, stride, seed, id0, id_step, bins, None if lo is None else lo.ctypes.data,
-            None if hi is None else hi.ctypes.data, thr.ctypes.data if tails is not None else None, ptr(counts), ptr(tails), ptr(extremes),
-            _stream(dev)), "glabc_predictive_counts")
+        fused.counts(h.data_ptr(), n_rows, d, stride, stride, seed, id0, id_step, bins, None if lo is None else lo.ctypes.data,
+                     None if hi is None else hi.ctypes.data, thr.ctypes.data if tails is not None else None, ptr(counts), ptr(tails),
+                     ptr(extremes), _stream(dev))
     to_u64 = lambda t: None if t is None else t.cpu().numpy().view(np.uint64)          # noqa: E731
     return to_u64(counts), to_u64(tails), None if extremes is None else extremes.cpu().numpy().view(np.uint32)
 
@@ -231,19 +273,18 @@ def _torch_range(stats):
 
 # ---------------------------------------------------------------------------------- the public surface
 def simulate(Model, history, *, seed, layout="rows", chain0=0, n_chains_total=None, row0=0):
-    """``glabc_predictive_draws`` -> (y_rep, distance): float32 device tensors in the history's layout -- y_rep (T, C, y_dim) and
+    """``glabc_predictive_draws`` (a CompiledModel: ``glabc_rtc_predictive_draws``) -> (y_rep, distance): float32 device tensors in the history's layout -- y_rep (T, C, y_dim) and
     distance (T, C) for a (T, C, D) history, (T, y_dim) and (T,) for (T, D), (T, y_dim, C) and (T, C) for layout="chain_major".
     Draw (t, c) has the id (row0 + t) * n_chains_total + chain0 + c and depends on (Model, theta, seed, id) only."""
     n, c, d = _history(Model, history, layout)
     _seed(seed)
     id0, id_step = _ids(c, chain0, n_chains_total, row0)
-    desc = _path(Model, history, "fused")
+    fused = _path(Model, history, "fused")
     h = diagnostics._chain_major(history, layout)
-    y = torch.empty(n, desc.y_dim, c, dtype=torch.float32, device=h.device)
+    y = torch.empty(n, fused.desc.y_dim, c, dtype=torch.float32, device=h.device)
     dis = torch.empty(n, c, dtype=torch.float32, device=h.device)
     with torch.cuda.device(h.device):
-        _capi.check(_capi.lib().glabc_predictive_draws(C.byref(desc), h.data_ptr(), n, d, c, c, engine.draw_seed(seed), id0, id_step,
-                                                       y.data_ptr(), c, dis.data_ptr(), c, _stream(h.device)), "glabc_predictive_draws")
+        fused.draws(h.data_ptr(), n, d, c, c, engine.draw_seed(seed), id0, id_step, y.data_ptr(), c, dis.data_ptr(), c, _stream(h.device))
     if layout == "chain_major":
         return y, dis
     if len(tuple(history.shape)) == 2:
@@ -256,19 +297,19 @@ def _tables(Model, history, bins, range, thresholds, seed, layout, chain0, n_cha
     bins = _bins(bins)
     _seed(seed)
     id0, id_step = _ids(c, chain0, n_chains_total, row0)
-    desc = _path(Model, history, path)
-    if desc is not None:
-        k = desc.y_dim + 1
+    fused = _path(Model, history, path)
+    if fused is not None:
+        k = fused.desc.y_dim + 1
         thr = _thresholds(Model, thresholds, k, True)
         lim = None if range is None else diagnostics._check_range(range, k)
         h = diagnostics._chain_major(history, layout)
         key = engine.draw_seed(seed)
         if lim is None:
-            _, tails, extremes = _fused_counts(desc, h, key, id0, id_step, bins, None, thr, ("tails", "extremes"))
+            _, tails, extremes = _fused_counts(fused, h, key, id0, id_step, bins, None, thr, ("tails", "extremes"))
             lim = _exact_range(extremes)
-            counts, _, _ = _fused_counts(desc, h, key, id0, id_step, bins, lim, thr, ("counts",))
+            counts, _, _ = _fused_counts(fused, h, key, id0, id_step, bins, lim, thr, ("counts",))
         else:
-            counts, tails, _ = _fused_counts(desc, h, key, id0, id_step, bins, lim, thr, ("counts", "tails"))
+            counts, tails, _ = _fused_counts(fused, h, key, id0, id_step, bins, lim, thr, ("counts", "tails"))
         return Terms(n * c, counts, tails, lim, thr, True)
     stats, has_distance = _generic_stats(Model, history, layout, seed)
     k = stats.shape[1]
@@ -324,6 +365,6 @@ def check(Model, history, *, bins=64, range=None, thresholds=None, seed, layout=
           path="auto"):
     """The posterior predictive check of a history -> Check (see ``summary``).  thresholds: K numbers, default ``y_obs`` for the
     coordinates and ``Model.epsilon`` for the distance.  range: (lo, hi) or (K, 2) -- one pass; None -- the exact minimum and
-    maximum of every statistic, found in a pass of its own.  path: "auto" (the kernel for descriptor Models and a history on the
-    GPU, else generic), "fused", "generic"."""
+    maximum of every statistic, found in a pass of its own.  path: "auto" (the kernel for descriptor Models and CompiledModels
+    and a history on the GPU, else generic), "fused", "generic"."""
     return summary(_tables(Model, history, bins, range, thresholds, seed, layout, chain0, n_chains_total, row0, path))

@@ -1038,6 +1038,50 @@ int glabc_rtc_smc_draws(const glabc_rtc_program* program, const glabc_model* mod
                         int64_t row0, const int64_t* ids, int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out,
                         float* log_prior_out, uint8_t* accept_out, void* stream);
 
+/* ---- The posterior predictive kernel around a USER simulator (csrc/glabc_rtc.hip): glabc_predictive_draws and glabc_predictive_counts
+ * for GLABC_SIM_USER Models.  glabc_rtc_compile_predictive compiles (hiprtc, gfx950) the template those two entry points are
+ * instantiated from -- predictive_kernel (csrc/glabc_predictive.h) -- around `simulator_source` (the source of glabc_rtc_compile, with
+ * its optional GLABC_USER_DISCREPANCY), plus the two row kernels every program holds: glabc_rtc_simulate, glabc_rtc_hooks,
+ * glabc_rtc_model_rows and glabc_rtc_release take a predictive program as any other.  It is a fourth kind of program beside the
+ * sampler, the mixture and the draws programs: glabc_rtc_steps, glabc_rtc_mix_steps, glabc_rtc_abc_draws and glabc_rtc_smc_draws
+ * refuse it with GLABC_ERR_KIND, and the two launch entry points below refuse those three kinds the same way.  The kernel walks
+ * the history one row per item whatever the source (csrc/glabc_rtc_predictive_kernels.h); a draw does not depend on that.  Compile
+ * options, the log and GLABC_ERR_ARG / GLABC_ERR_NO_DEVICE are glabc_rtc_compile's; a kernel that spills registers or keeps a private
+ * segment is named in the log and handed out.  Refusals of glabc_rtc_compile_predictive, in this order:
+ *   a NULL source or out                                                                          GLABC_ERR_NULL
+ *   theta_dim, y_dim or noise_dim outside 1 .. GLABC_MAX_DIM                                      GLABC_ERR_DIM
+ *   a source that does not compile (see the log)                                                  GLABC_ERR_ARG
+ * A source that announces GLABC_USER_PRIOR is accepted: theta comes from the history, the prior is never evaluated -- and for the
+ * same reason a Gamma or a user prior in the descriptor is no ground for refusal at launch.
+ *
+ * Ids, layouts, NULL outputs, the tables, thresholds, extremes, bins and the LDS table of at most 36 972 bytes of
+ * glabc_rtc_predictive_draws / glabc_rtc_predictive_counts are glabc_predictive_draws' / glabc_predictive_counts'.  Specification of
+ * draw (row t, chain c), id = id0 + t * id_step + c, a composition of entry points of this header (nd = noise_dim):
+ *     theta = history[t][.][c]
+ *     eps   = row id of glabc_dist_forward(a DiagGaussian of dimension nd, location 0 and scale 1, ., seed ^ GLABC_PREDICTIVE_KEY, .):
+ *             per history row t one call with row0 = id0 + t * id_step, n = n_chains
+ *     y     = glabc_rtc_simulate(program, theta, eps)
+ *     dis   = glabc_rtc_model_rows(program, model, GLABC_RTC_DISCREPANCY, y) where the source announces GLABC_USER_DISCREPANCY,
+ *             else glabc_model_discrepancy(model, y)
+ * Refusals of the two, in this order; a refused call launches nothing and writes nothing:
+ *   a NULL program or model                                                                       GLABC_ERR_NULL
+ *   model->sim_kind != GLABC_SIM_USER                                                             GLABC_ERR_KIND
+ *   a program that glabc_rtc_compile_predictive did not make                                      GLABC_ERR_KIND
+ *   model->theta_dim, y_dim or noise.dim differ from the program's                                GLABC_ERR_DIM
+ *   everything glabc_predictive_draws / glabc_predictive_counts refuse, in their order (of the Model, what is left is
+ *     theta_dim != model->theta_dim: GLABC_ERR_DIM)
+ * n_chains == 0 returns GLABC_OK and writes nothing.  glabc_predictive_draws and glabc_predictive_counts keep refusing
+ * GLABC_SIM_USER.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no struct changes. */
+int glabc_rtc_compile_predictive(const char* simulator_source, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
+                                 glabc_rtc_program** out, char* log, int64_t log_size);
+int glabc_rtc_predictive_draws(const glabc_rtc_program* program, const glabc_model* model, const float* history, int64_t n_rows,
+                               int32_t theta_dim, int64_t n_chains, int64_t stride, uint64_t seed, int64_t id0, int64_t id_step,
+                               float* y_out, int64_t y_stride, float* dis_out, int64_t dis_stride, void* stream);
+int glabc_rtc_predictive_counts(const glabc_rtc_program* program, const glabc_model* model, const float* history, int64_t n_rows,
+                                int32_t theta_dim, int64_t n_chains, int64_t stride, uint64_t seed, int64_t id0, int64_t id_step,
+                                int32_t n_bins, const double* lo, const double* hi, const float* threshold, uint64_t* counts,
+                                uint64_t* tails, uint32_t* extremes, void* stream);
+
 /* AGLMCMC.py:199-204 (and :104-109): weights of a proposal pool from its stored discrepancies,
  * w[r] = exp((prior(theta_r) + calculate_log_kernel_dis(dis_r)) - log_q[r]), NaN -> 0.  The threshold is the one in
  * model->kern_* (the caller passes a copy of its descriptor with the annealed eps_hat, Mixture.py:47-53).
