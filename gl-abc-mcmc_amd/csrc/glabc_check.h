@@ -312,6 +312,32 @@ inline int check_cross_moments(const float* history, int64_t n_rows, int32_t the
     return check_autocov(history, n_rows, theta_dim, n_chains, stride, 0, mean_out, cov_out);
 }
 
+// ---- glabc_weighted_gram / glabc_regression_apply: the dimension-major rows of glabc_abc_draws, in the order include/glabc.h lists
+// the refusals.  Both dimensions are free in 1 .. GLABC_MAX_DIM; a NaN delta fails `delta > 0`, +inf passes
+inline int check_regress_dims(int32_t theta_dim, int32_t y_dim)
+{
+    return (theta_dim < 1 || theta_dim > GLABC_MAX_DIM || y_dim < 1 || y_dim > GLABC_MAX_DIM) ? GLABC_ERR_DIM : GLABC_OK;
+}
+
+inline int check_weighted_gram(const float* theta, int64_t stride_t, int32_t theta_dim, const float* y, int64_t stride_y, int32_t y_dim,
+                               int64_t n, const double* y_obs, double delta, int32_t kind, const double* gram, const double* workspace)
+{
+    if (!theta || !y || !y_obs || !gram || (!workspace && n > 0)) return GLABC_ERR_NULL;
+    if (int e = check_regress_dims(theta_dim, y_dim)) return e;
+    if (kind != GLABC_GRAM_EPANECHNIKOV && kind != GLABC_GRAM_UNIFORM) return GLABC_ERR_KIND;
+    if (n < 0 || stride_t < n || stride_y < n || !(delta > 0.0)) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
+inline int check_regression_apply(const float* theta, int64_t stride_t, int32_t theta_dim, const float* y, int64_t stride_y, int32_t y_dim,
+                                  int64_t n, const double* y_obs, const double* beta, const float* out, int64_t stride_o)
+{
+    if (!theta || !y || !y_obs || !beta || !out) return GLABC_ERR_NULL;
+    if (int e = check_regress_dims(theta_dim, y_dim)) return e;
+    if (n < 0 || stride_t < n || stride_y < n || stride_o < n) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
 // ---- glabc_abc_draws: the Model a fused rejection draw is compiled for and the range of draws, in the order include/glabc.h lists
 // the refusals.  The parameters' values are not looked at: a draw from a prior of scale 0 or NaN is what the arithmetic says it is
 // the shapes the built-in simulators are compiled for, then the simulator's kind; theta_dim: what the caller's data has (a history's;

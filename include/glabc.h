@@ -1082,6 +1082,58 @@ int glabc_rtc_predictive_counts(const glabc_rtc_program* program, const glabc_mo
                                 int32_t n_bins, const double* lo, const double* hi, const float* threshold, uint64_t* counts,
                                 uint64_t* tails, uint32_t* extremes, void* stream);
 
+/* ---- ABC regression adjustment (Beaumont, Zhang and Balding 2002; csrc/glabc_regress.hip, glabcmcmc_amd/regression.py): the weighted
+ * second moments of n kept draws, from which the host fits theta = alpha + B^T (y - y_obs) + e, and the row-wise correction
+ * theta - B^T (y - y_obs).  The rows are what glabc_abc_draws writes, float32 and dimension-major, read in place:
+ *     theta[j * stride_t + r]   j < theta_dim          y[k * stride_y + r]   k < y_dim          dis[r]          weight[r]
+ * Columns n .. stride - 1 are never read.  theta_dim and y_dim are each 1 .. GLABC_MAX_DIM and independent of one another.  dis and
+ * weight are device arrays, each of which may be NULL; y_obs (and beta below) are HOST arrays.  The entry points allocate nothing.
+ *
+ * glabc_weighted_gram.  With P = 1 + y_dim + theta_dim, row r has the design vector
+ *     z_r = (1.0, (double) y_r,0 - y_obs_0, .., (double) y_r,y_dim-1 - y_obs_y_dim-1, (double) theta_r,0, .., (double) theta_r,theta_dim-1)
+ * and gram[Q], Q = P (P + 1) / 2 + 1 doubles on the device, holds the packed upper triangle of sum_r w_r z_r z_r^T,
+ *     gram[q],   q = a * P - a (a - 1) / 2 + (b - a),   a <= b < P           (the packing of glabc_cross_moments)
+ * and, last, gram[Q - 1] = sum_r w_r^2 (for Kish's effective sample size).  workspace: ceil(n / GLABC_GRAM_SEGMENT) * Q doubles on
+ * the device, the caller's (it may be NULL when n == 0); its contents afterwards are the segments' partial sums.
+ *
+ * Numerical specification.  All arithmetic is IEEE double, every line one rounded operation in the stated order, no FMA.
+ *     d = (double) dis_r;    u = d / delta
+ *     GLABC_GRAM_EPANECHNIKOV:  k = d <= delta ? 1.0 - u * u : 0.0          GLABC_GRAM_UNIFORM:  k = d <= delta ? 1.0 : 0.0
+ *     dis == NULL:  k = 1.0                                                 w_r = weight ? k * (double) weight_r : k
+ * A NaN distance fails the comparison: k = 0.  delta = +inf is legal and keeps every finite distance with k = 1 (u = 0).
+ *     term_r of statistic (a, b):  (w_r * z_r,a) * z_r,b                    term_r of the last statistic:  w_r * w_r
+ * A row with w_r == 0.0 contributes NOTHING: it is skipped, not multiplied, so a NaN theta or y in a row outside the tolerance
+ * poisons nothing.  A NaN w_r is not 0: it propagates into every statistic, and a NaN or an infinity in z of a weighted row into the
+ * statistics that involve the coordinate, as the lines say.  The order of the sums does not depend on the launch geometry:
+ *     segment s covers rows 1024 s .. 1024 s + 1023 (GLABC_GRAM_SEGMENT); column l < 64 of a segment is
+ *         c_l = 0.0;  for t = 0 .. 15:  r = 1024 s + 64 t + l;  if r < n and w_r != 0.0:  c_l = c_l + term_r
+ *     then for h = 1, 2, 4, 8, 16, 32, all columns at once:  c_l = c_l + c_(l xor h)      (every column ends with the same bits)
+ *     partial_s = c_0;        G = 0.0;  for s ascending:  G = G + partial_s
+ * so a NumPy loop reproduces gram bit for bit (tests/regress_ref.py).  Two launches on the caller's stream: the segments, then one
+ * workgroup that adds the partial sums.  n == 0 returns GLABC_OK and writes Q zeros.
+ * Refusals, in this order; a refused call launches nothing and writes nothing:
+ *   a NULL theta, y, y_obs or gram; a NULL workspace with n > 0                                   GLABC_ERR_NULL
+ *   theta_dim or y_dim outside 1 .. GLABC_MAX_DIM                                                 GLABC_ERR_DIM
+ *   a kind that is neither GLABC_GRAM_EPANECHNIKOV nor GLABC_GRAM_UNIFORM                         GLABC_ERR_KIND
+ *   n < 0, stride_t < n, stride_y < n, a delta that is NaN or <= 0                                GLABC_ERR_ARG
+ *
+ * glabc_regression_apply.  For every row r < n and every j < theta_dim, with beta[k * theta_dim + j] the HOST array B of the fit:
+ *     a = (double) theta_r,j;   for k = 0 .. y_dim - 1 ascending:  a = a - beta[k * theta_dim + j] * ((double) y_r,k - y_obs_k)
+ *     out[j * stride_o + r] = (float) a
+ * (each subtraction and each product rounded once, no FMA).  Every row is corrected, whatever its weight.  `out` may be `theta`
+ * itself with stride_o == stride_t (in place) and nothing else that overlaps an input; columns n .. stride_o - 1 are not written.
+ * Refusals, in this order: a NULL pointer GLABC_ERR_NULL; theta_dim or y_dim outside 1 .. GLABC_MAX_DIM GLABC_ERR_DIM; n < 0 or a
+ * stride < n GLABC_ERR_ARG.  n == 0 returns GLABC_OK and writes nothing.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged by
+ * both: no struct changes. */
+#define GLABC_GRAM_EPANECHNIKOV 0
+#define GLABC_GRAM_UNIFORM 1
+#define GLABC_GRAM_SEGMENT 1024
+int glabc_weighted_gram(const float* theta, int64_t stride_t, int32_t theta_dim, const float* y, int64_t stride_y, int32_t y_dim,
+                        const float* dis, const float* weight, int64_t n, const double* y_obs, double delta, int32_t kind, double* gram,
+                        double* workspace, void* stream);
+int glabc_regression_apply(const float* theta, int64_t stride_t, int32_t theta_dim, const float* y, int64_t stride_y, int32_t y_dim,
+                           int64_t n, const double* y_obs, const double* beta, float* out, int64_t stride_o, void* stream);
+
 /* AGLMCMC.py:199-204 (and :104-109): weights of a proposal pool from its stored discrepancies,
  * w[r] = exp((prior(theta_r) + calculate_log_kernel_dis(dis_r)) - log_q[r]), NaN -> 0.  The threshold is the one in
  * model->kern_* (the caller passes a copy of its descriptor with the annealed eps_hat, Mixture.py:47-53).
