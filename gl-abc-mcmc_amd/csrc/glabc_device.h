@@ -706,8 +706,9 @@ GLABC_DEV float fast_expf(float x)
 GLABC_DEV float fast_logf(float x) { return 0.6931471805599453f * __builtin_amdgcn_logf(x); }       // log(0) = -inf
 
 // ---- iSIR weights, GLMCMC.py:78-81 ------------------------------------------------------------
-// isir_weight: the specified weight, glabc_expf with NaN -> 0.  These are the bits the chain carries (w_cur) and the bits
-// the IEEE index search divides.
+// isir_weight: the specified weight, glabc_expf with NaN -> 0.  These are the bits the IEEE index search divides; it takes
+// them from the log-weights (the current state's from lw_cur), so the weight a chain carries between iterations (w_cur)
+// may be the stand-in.
 // isir_weight_approx: a stand-in read ONLY by the float32 fast pass of the index search (chain_step, team_sampler_kernel),
 // whose margin absorbs it: the spec's exact reduction x = k ln2 + r, the hardware 2^(r log2e) (v_exp_f32 on |arg| <= 1/2)
 // and an exact scaling by 2^k (v_ldexp_f32, which rounds once, into the denormals too).  For EVERY float argument
@@ -801,7 +802,8 @@ struct Chain {
     float q;          // global/importance log_prob(theta)  (cache)
     float log_w;      // log_weight_old, GLMCMC.py:53-55 -- stale after an accepted local move until the next global step
     float lw_cur;     // (prior + kern) - q of the CURRENT state: what GLMCMC.py:60-64 will assign to log_weight_old (cache)
-    float w_cur;      // exp(lw_cur), NaN -> 0: the current state's iSIR weight, GLMCMC.py:75-81 (cache)
+    float w_cur;      // exp(lw_cur), NaN -> 0: the current state's iSIR weight, GLMCMC.py:75-81 (cache); after a move the
+                      // winner's isir_weight_approx where the fast index pass uses that, never stored
     float gf;         // this chain's global_frequency
     uint32_t flags;
     uint32_t n_moves;
@@ -1033,9 +1035,11 @@ GLABC_DEV bool chain_step(const typename KernelArgs<D, YD, VAR>::type& a, const 
         // weight_sampling, GLMCMC.py:17-22: first k with u < sum_{j<=k} (double)(w_j / tot).  Fast pass in float32:
         // w_j * rcp(tot) is within 2.4e-7 relative of the float32 quotient (1 ulp of v_rcp_f32 + one rounding) and a
         // float32 running sum of <= 17 such terms adds <= 1e-6, so the partial sums are within 1.3e-6 of the reference's
-        // and the index can differ only if u lies that close to one of them.  The candidates' weights of this pass are
-        // isir_weight_approx (w_cur is exact): each within 1e-6 relative + 2^-149 of the specified one, so a partial sum
-        // S_k and the total T are within 1e-6 relative + 17 * 2^-149, and S_k / T within 2.0e-6 + 34 * 2^-149 / T of the
+        // and the index can differ only if u lies that close to one of them.  ALL N + 1 <= 17 weights of this pass may be
+        // isir_weight_approx -- the candidates' always, w_cur from the chain's first move of the launch on (at kernel
+        // entry it is the specified one, which satisfies the same bound): each within 1e-6 relative + 2^-149 of the
+        // specified one, so a partial sum S_k and the total T are within 1e-6 relative + 17 * 2^-149 (one term per weight,
+        // the current state's included), and S_k / T within 2.0e-6 + 34 * 2^-149 / T of the
         // quotient of the specified weights -- 2.0e-6 once T >= 2^-100.  1.3e-6 + 2.0e-6 < 4e-6: lanes where
         // |u - partial sum| <= 4e-6 somewhere, or T is below 2^-100, at least 2^126 or NaN, redo it the reference's way:
         // the specified weights, IEEE divisions, double sums.
@@ -1065,6 +1069,7 @@ GLABC_DEV bool chain_step(const typename KernelArgs<D, YD, VAR>::type& a, const 
                 gather_weights<L, N, NL>(lw, lwg);
 #pragma unroll
                 for (int k = 1; k <= N; ++k) w[k] = isir_weight(lwg[k]);
+                w[0] = isir_weight(c.lw_cur);                                 // w_cur may be the fast one (the move below)
                 tot = aten_rowsum<N + 1>(w);
             }
             ig = -1;
@@ -1089,7 +1094,12 @@ GLABC_DEV bool chain_step(const typename KernelArgs<D, YD, VAR>::type& a, const 
         const int slot = (ind - 1) / L;
         // this lane's candidate in the winning slot (conditional moves over the unrolled slots keep
         // everything in VGPRs; a run-time array index would be promoted to LDS / scratch)
-        constexpr bool CARRY_W = (ALGO == ALGO_GLMCMC) && !kFastPassWeights;  // wl holds the specified weights
+        // The winner's wl becomes w_cur: the specified weight where wl holds it (run-time compiled kernels), else the fast
+        // pass's stand-in, which only the fast pass reads.  The IEEE fallback takes isir_weight(c.lw_cur) instead, and lw_cur
+        // is the log-weight of exactly that weight on every path: w_cur and lw_cur are assigned together here (a global
+        // move and an accepted local move alike: slot 0's lw / wl are the proposed state's own, see above) and at kernel
+        // entry, and the local-flag hand-over of GLMCMC.py:60-64 copies lw_cur into log_w without touching either.
+        constexpr bool CARRY_W = (ALGO == ALGO_GLMCMC);
         float nt[D], ny[YD], nlw = lw[0], npr = pr[0], nkk = kk[0], nw = CARRY_W ? wl[0] : 0.0f;
 #pragma unroll
         for (int q = 0; q < D; ++q) nt[q] = th[0][q];
@@ -1139,7 +1149,7 @@ GLABC_DEV bool chain_step(const typename KernelArgs<D, YD, VAR>::type& a, const 
                 c.q = dist_log_prob<D, GU, GM>(a.global, c.theta);
             if (ALGO == ALGO_GLMCMC) {
                 c.lw_cur = nlw;
-                c.w_cur = CARRY_W ? nw : isir_weight(nlw);                    // the specified weight, never the fast one
+                c.w_cur = nw;                                                 // wl of nlw's candidate (CARRY_W above)
                 if (is_global)
                     c.log_w = nlw;                                            // GLMCMC.py:86
                 else

@@ -199,6 +199,8 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
         const float v = FAST ? fast_expf(c.lw_cur) : glabc_expf(c.lw_cur);
         c.w_cur = (v != v) ? 0.0f : v;                                                      // GLMCMC.py:78-81
     }
+    // From the first move on w_cur is the winner's fast-pass weight (below); the index fallback recomputes the specified one from
+    // lw_cur, which is set with w_cur here and at the move and nowhere else (the hand-over to log_w only reads it): chain_step.
     constexpr int TRI = D * (D + 1) / 2;
     const bool mom = a.sum_theta != nullptr;
     double s1[D], s2[TRI], sj[TRI];
@@ -263,19 +265,26 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
         {
             const float rinv = __builtin_amdgcn_rcpf(tot);
             const float u32 = (float)u_res;
-            float run = 0.0f;
+            // chain_step's pass in fewer instructions (every build of this kernel: FAST and run-time compiled ones too).  The terms are >= 0 or NaN, so `run` never decreases and `gap` never
+            // increases: the first k with gap < 0 is the NUMBER of gaps >= 0 (N + 1: none, stay), and every |gap| exceeds the
+            // margin iff the smallest does.  A NaN term (a zero or non-finite total) would be skipped by both the count and the
+            // minimum, but it makes every later `run` NaN, the last one too, and the test of `run` below then refuses the lane.
+            float run = 0.0f, nearest = __builtin_inff();
+            int cnt = 0;
 #pragma unroll
             for (int k = 0; k <= N; ++k) {
                 run += w[k] * rinv;
                 const float gap = u32 - run;
-                sure = sure && (__builtin_fabsf(gap) > 4e-6f);
-                ig = (ig < 0 && gap < 0.0f) ? k : ig;
+                nearest = __builtin_fminf(nearest, __builtin_fabsf(gap));
+                cnt += (gap >= 0.0f) ? 1 : 0;
             }
-            sure = sure && (run > 0.999f) && (run < 1.001f);
+            ig = cnt > N ? -1 : cnt;
+            sure = sure && (nearest > 4e-6f) && (run > 0.999f) && (run < 1.001f);
             if constexpr (!FAST && kFastPassWeights) sure = sure && (tot >= 0x1p-100f) && (tot < 0x1p126f);   // chain_step's bound
         }
         if (!sure) {
             if constexpr (!FAST && kFastPassWeights) {                            // the specified weights (helpers' from LDS)
+                w[0] = isir_weight(c.lw_cur);                                     // w_cur may be the fast one (chain_step)
 #pragma unroll
                 for (int r = 0; r < NA; ++r) w[1 + r] = isir_weight(lw[r]);
 #pragma unroll
@@ -334,7 +343,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
                 c.kern = nkk;
                 c.q = dist_log_prob<D, GU, GM>(a.global, c.theta);
                 c.lw_cur = nlw;
-                c.w_cur = (FAST || !kFastPassWeights) ? nw : isir_weight(nlw);    // never the fast pass's weight
+                c.w_cur = nw;                                                     // the fast pass's weight of nlw (chain_step)
                 if (is_global)
                     c.log_w = nlw;                                                // GLMCMC.py:86
                 else
