@@ -312,6 +312,38 @@ inline int check_cross_moments(const float* history, int64_t n_rows, int32_t the
     return check_autocov(history, n_rows, theta_dim, n_chains, stride, 0, mean_out, cov_out);
 }
 
+// ---- glabc_weighted_key_counts / glabc_weighted_histogram / glabc_weighted_histogram2d: the twins' refusals in the twins' order on
+// the one-row history [1][dim][stride] of n draws (a null weight array is a null pointer like the others), then what the weights
+// add: more than GLABC_MAX_WEIGHTED_DRAWS draws (n < 0 and stride < n are the twins' own), a scale that is not finite or not > 0
+inline int check_weight_scale(int64_t n, double scale)
+{
+    return (n > GLABC_MAX_WEIGHTED_DRAWS || !std::isfinite(scale) || !(scale > 0.0)) ? GLABC_ERR_ARG : GLABC_OK;
+}
+
+inline int check_weighted_key_counts(const float* x, int64_t stride, int32_t dim, const float* w, int64_t n, double scale, int32_t level,
+                                     int32_t n_prefixes, const uint32_t* prefixes, const uint64_t* counts)
+{
+    if (!w) return GLABC_ERR_NULL;
+    if (int e = check_key_counts(x, 1, dim, n, stride, level, n_prefixes, prefixes, counts)) return e;
+    return check_weight_scale(n, scale);
+}
+
+inline int check_weighted_histogram(const float* x, int64_t stride, int32_t dim, const float* w, int64_t n, double scale, int32_t n_bins,
+                                    const double* lo, const double* hi, const uint64_t* counts)
+{
+    if (!w) return GLABC_ERR_NULL;
+    if (int e = check_histogram(x, 1, dim, n, stride, n_bins, lo, hi, counts)) return e;
+    return check_weight_scale(n, scale);
+}
+
+inline int check_weighted_histogram2d(const float* x, int64_t stride, int32_t dim, const float* w, int64_t n, double scale, int32_t n_pairs,
+                                      const int32_t* pairs, int32_t n_bins, const double* lo, const double* hi, const uint64_t* counts)
+{
+    if (!w) return GLABC_ERR_NULL;
+    if (int e = check_histogram2d(x, 1, dim, n, stride, n_pairs, pairs, n_bins, lo, hi, counts)) return e;
+    return check_weight_scale(n, scale);
+}
+
 // ---- glabc_weighted_gram / glabc_regression_apply: the dimension-major rows of glabc_abc_draws, in the order include/glabc.h lists
 // the refusals.  Both dimensions are free in 1 .. GLABC_MAX_DIM; a NaN delta fails `delta > 0`, +inf passes
 inline int check_regress_dims(int32_t theta_dim, int32_t y_dim)

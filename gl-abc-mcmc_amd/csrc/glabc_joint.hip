@@ -5,7 +5,7 @@
 // blockIdx.y is the pair; the walk over items of 64 chains x JOINT_ROWS rows, the guarded loads, the uint32 table in LDS, the grid
 // rule and glabc_histogram's bin arithmetic are glabc_history.h's, which argues what cannot be read, that a slot is inside the table
 // and that no counter wraps.  An item loads the row segments of both coordinates, all 2 x JOINT_ROWS loads issued together, and a
-// lane outside the segment counts nothing.  Each value is binned on its own axis (axis_bin) and the two bins make the slot: n_bins^2 + 2
+// lane outside the segment counts nothing.  Each value is binned on its own axis (axis_bin, glabc_slots.h) and the two bins make the slot: n_bins^2 + 2
 // counters.  At 128 bins the table is 65 544 bytes: past what a launch gets unasked, so the launcher has the size granted
 // (glabc_lds_grant.h) as the lane-group and the flow launchers do; two workgroups share a CU then.
 // Contention.  One LDS atomic per draw.  A grid of bins spreads a posterior over far more counters than a level-0 digit table
@@ -29,37 +29,13 @@
 #include "glabc_history.h"
 #include "glabc_launch.h"
 #include "glabc_lds_grant.h"
+#include "glabc_slots.h"
 
 namespace glabc {
 
 constexpr int JOINT_ROWS = 8;           // rows per item: the 16 loads of both coordinates in flight together, as count_kernel's 16
                                         // (16 rows are 32 descriptors, more than the scalar file holds without spilling)
 constexpr int64_t JOINT_MAX_ITEMS_PER_WAVE = 1 << 19;    // x HISTORY_WAVES x JOINT_ROWS x HISTORY_LANES = 2^31 draws per workgroup
-
-constexpr int AXIS_OUTSIDE = -1, AXIS_NAN = -2;
-
-struct JointSlots {
-    double lo[GLABC_MAX_DIM], hi[GLABC_MAX_DIM], scale[GLABC_MAX_DIM];
-    int32_t n_bins;
-    uint8_t a[GLABC_MAX_PAIRS], b[GLABC_MAX_PAIRS];
-};
-
-// the bin of a value on an axis, glabc_histogram's rule; AXIS_OUTSIDE below lo or above hi, AXIS_NAN
-__device__ __forceinline__ int axis_bin(float xf, const BinAxis& a, int n_bins)
-{
-    const double x = (double)xf;
-    if (x != x) return AXIS_NAN;
-    if (x < a.lo || x > a.hi) return AXIS_OUTSIDE;
-    return bin_inside(x, a, n_bins);
-}
-
-// a NaN on either axis before a value outside on either axis before the cell
-__device__ __forceinline__ int joint_slot(int bin_a, int bin_b, int n_bins)
-{
-    const int least = bin_a < bin_b ? bin_a : bin_b;
-    const int cells = n_bins * n_bins;
-    return least >= 0 ? bin_a * n_bins + bin_b : least == AXIS_NAN ? cells + 1 : cells;
-}
 
 __global__ void __launch_bounds__(HISTORY_LANES* HISTORY_WAVES)
     joint_kernel(const float* __restrict__ hist, int64_t n_rows, int64_t row_step, int64_t n_chains, int64_t stride, const JointSlots slots,
@@ -113,18 +89,7 @@ static_assert(joint_grid(1 << 18, 28, 1 << 20, 65544) == 128 && joint_grid(1 << 
 inline int launch_joint(const float* history, int64_t n_rows, int32_t theta_dim, int64_t n_chains, int64_t stride, int32_t n_pairs,
                         const int32_t* pairs, int32_t n_bins, const double* lo, const double* hi, uint64_t* counts, hipStream_t s)
 {
-    JointSlots j;
-    for (int q = 0; q < GLABC_MAX_DIM; ++q) j.lo[q] = 0.0, j.hi[q] = 1.0, j.scale[q] = 1.0;          // a coordinate no pair uses
-    for (int p = 0; p < GLABC_MAX_PAIRS; ++p) {
-        j.a[p] = (uint8_t)(p < n_pairs ? pairs[2 * p] : 0);
-        j.b[p] = (uint8_t)(p < n_pairs ? pairs[2 * p + 1] : 0);
-    }
-    for (int q = 0; q < 2 * n_pairs; ++q) {
-        const int c = pairs[q];
-        const BinAxis a = bin_axis(lo[c], hi[c], n_bins);
-        j.lo[c] = a.lo, j.hi[c] = a.hi, j.scale[c] = a.scale;
-    }
-    j.n_bins = n_bins;
+    const JointSlots j = joint_slots(n_pairs, pairs, n_bins, lo, hi);
     const size_t lds_bytes = ((size_t)n_bins * n_bins + 2) * sizeof(uint32_t);
     static LdsGrant grant;                               // per device
     if (!grant_dynamic_lds(grant, (const void*)joint_kernel, lds_bytes)) return GLABC_ERR_LAUNCH;

@@ -1,6 +1,6 @@
 // glabc_quant.hip -- integer counts over a chain-major history: the digit counts of a radix selection (glabc_key_counts) and
 // marginal histograms (glabc_histogram) of include/glabc.h, which holds the specification.  One counting skeleton, the slot
-// function (which counter a value adds to, or none) as a template parameter.  No template over theta_dim: the coordinate is a
+// function (which counter a value adds to, or none; glabc_slots.h) as a template parameter.  No template over theta_dim: the coordinate is a
 // grid dimension, as in glabc_diag.hip.
 //
 // count_kernel.  Lanes run along the chain index and blockIdx.y is the coordinate.  The walk over items of 64 chains x CHUNK_ROWS
@@ -20,6 +20,7 @@
 #include "glabc_check.h"
 #include "glabc_history.h"
 #include "glabc_launch.h"
+#include "glabc_slots.h"
 
 namespace glabc {
 
@@ -27,55 +28,6 @@ constexpr int CHUNK_ROWS = 16;          // rows per item, their loads in flight 
 constexpr int64_t MAX_ITEMS_PER_WAVE = 1 << 18;          // x HISTORY_WAVES x CHUNK_ROWS x HISTORY_LANES = 2^31 values per workgroup
 
 enum CountMode { COUNT_DIRECT = 0, COUNT_RUNS = 1 };
-
-// ---- slot functions: value -> index of its counter in the coordinate's table, or -1 -------------------------------------------
-// NP: 0 at level 0, where every value belongs and nothing is compared; otherwise the prefixes compared per value -- n_prefixes
-// rounded up to 1, 2, 4 or 8, the slots past n_prefixes unused.  Two vector instructions per prefix and value: the kernel is bound
-// by its vector instructions before it is bound by HBM, so a launch pays for the prefixes it has
-template <int NP>
-struct KeySlots {
-    uint32_t prefix[GLABC_MAX_DIM][NP ? NP : 1];
-    int32_t n_prefixes, prefix_shift, digit_shift, digit_bits;   // prefix_shift: 32 - prefix_bits
-
-    __device__ int n_slots() const { return n_prefixes << digit_bits; }
-    // the coordinate's prefixes, from the kernel arguments into scalar registers
-    struct Local {
-        uint32_t p[NP ? NP : 1];
-        int32_t prefix_shift, digit_shift, digit_bits;
-        __device__ int operator()(float x) const
-        {
-            const uint32_t k = float_key(x);
-            const int digit = (int)((k >> digit_shift) & ((1u << digit_bits) - 1u));
-            if (NP == 0) return digit;
-            const uint32_t mine = k >> prefix_shift;
-            int slot = -1;
-#pragma unroll
-            for (int s = 0; s < NP; ++s) slot = mine == p[s] ? s : slot;          // an unused slot matches no prefix
-            return slot < 0 ? -1 : (slot << digit_bits) | digit;
-        }
-    };
-    __device__ Local local(int j) const
-    {
-        Local l;
-#pragma unroll
-        for (int s = 0; s < (NP ? NP : 1); ++s) l.p[s] = prefix[j][s];
-        l.prefix_shift = prefix_shift, l.digit_shift = digit_shift, l.digit_bits = digit_bits;
-        return l;
-    }
-};
-
-struct HistSlots {
-    double lo[GLABC_MAX_DIM], hi[GLABC_MAX_DIM], scale[GLABC_MAX_DIM];
-    int32_t n_bins;
-
-    __device__ int n_slots() const { return n_bins + 3; }
-    struct Local {
-        BinAxis axis;
-        int32_t n_bins;
-        __device__ int operator()(float x) const { return hist_slot(x, axis, n_bins); }
-    };
-    __device__ Local local(int j) const { return Local{{lo[j], hi[j], scale[j]}, n_bins}; }
-};
 
 template <class Slots, int MODE>
 __global__ void __launch_bounds__(HISTORY_LANES* HISTORY_WAVES)
@@ -147,20 +99,6 @@ inline int launch_count(const float* history, int64_t n_rows, int32_t theta_dim,
     return launch_status();
 }
 
-template <int NP>
-inline KeySlots<NP> key_slots(int32_t theta_dim, int32_t level, int32_t n_prefixes, const uint32_t* prefixes)
-{
-    KeySlots<NP> k;
-    for (int j = 0; j < GLABC_MAX_DIM; ++j)
-        for (int s = 0; s < (NP ? NP : 1); ++s)
-            k.prefix[j][s] = NP && j < theta_dim && s < n_prefixes ? prefixes[j * n_prefixes + s] : KEY_UNUSED_SLOT;
-    k.n_prefixes = n_prefixes;
-    k.prefix_shift = 32 - key_prefix_bits(level);               // level 0 (NP == 0) never shifts by it
-    k.digit_bits = key_digit_bits(level);
-    k.digit_shift = 32 - key_prefix_bits(level) - k.digit_bits;
-    return k;
-}
-
 // what a wavefront does about equal slots: folding runs pays at level 0 alone, where a chain stays on one digit
 // for rows on end; at levels 1 and 2, where few values belong to a prefix, the two modes take the same time
 constexpr int COUNT_MODE = COUNT_DIRECT;
@@ -208,13 +146,8 @@ __attribute__((visibility("default"))) int glabc_histogram(const float* history,
 {
     if (int e = check_histogram(history, n_rows, theta_dim, n_chains, stride, n_bins, lo, hi, counts)) return e;
     if (n_chains == 0) return GLABC_OK;
-    HistSlots h;
-    for (int j = 0; j < GLABC_MAX_DIM; ++j) {
-        const BinAxis a = j < theta_dim ? bin_axis(lo[j], hi[j], n_bins) : bin_axis(0.0, 1.0, n_bins);
-        h.lo[j] = a.lo, h.hi[j] = a.hi, h.scale[j] = a.scale;
-    }
-    h.n_bins = n_bins;
-    return launch_count<HistSlots, COUNT_MODE>(history, n_rows, theta_dim, n_chains, stride, h, n_bins + 3, counts, (hipStream_t)stream);
+    return launch_count<HistSlots, COUNT_MODE>(history, n_rows, theta_dim, n_chains, stride, hist_slots(theta_dim, n_bins, lo, hi), n_bins + 3, counts,
+                                               (hipStream_t)stream);
 }
 
 }  // extern "C"

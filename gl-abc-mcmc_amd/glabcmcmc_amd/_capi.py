@@ -356,6 +356,12 @@ ENTRY_POINTS = {
                                       C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_regression_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "glabc_weighted_key_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glabc_weighted_histogram": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glabc_weighted_histogram2d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_selftest_numerics": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "glabc_selftest_sqrt": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "glabc_selftest_rowsum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

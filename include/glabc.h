@@ -1134,6 +1134,40 @@ int glabc_weighted_gram(const float* theta, int64_t stride_t, int32_t theta_dim,
 int glabc_regression_apply(const float* theta, int64_t stride_t, int32_t theta_dim, const float* y, int64_t stride_y, int32_t y_dim,
                            int64_t n, const double* y_obs, const double* beta, float* out, int64_t stride_o, void* stream);
 
+/* ---- summaries of weighted draws (csrc/glabc_weighted.hip, glabcmcmc_amd/weighted.py): the digit counts of a radix selection,
+ * marginal histograms and pair histograms of n draws with one float32 weight each -- an ABC-SMC population, regression-adjusted
+ * draws.  The draws are dimension-major float32 as glabc_weighted_gram reads them, x[j * stride + i], j < dim, i < n, stride >= n;
+ * columns n .. stride - 1 are never read and the base needs 4-byte alignment only.  w[i] is a device array of n float32 weights,
+ * `scale` a positive finite double of the host's.
+ *
+ * The quantised weight.  A draw counts with the integer multiplicity m of its weight w; IEEE double, no FMA:
+ *     v = (double) w * scale                                       one rounded product
+ *     m = 0                   if !(w > 0)                           zero, negative and NaN weights count nothing
+ *     m = 2^32 - 1            if v >= 4294967295.0
+ *     m = (uint64) rint(v)    otherwise                             ties to even
+ * A draw with m == 0 is skipped whatever its coordinates hold, a NaN included (glabc_weighted_gram skips a row of weight 0 in the
+ * same way).  A weighted quantile is then an ordinary order statistic of the multiset in which draw i occurs m_i times.  The counts
+ * are sums of integers: the same bits whatever the launch geometry and the order of the atomic adds, additive over slices of draws,
+ * and -- n <= GLABC_MAX_WEIGHTED_DRAWS = 2^31 draws of at most 2^32 - 1 each -- below 2^63, so no uint64 wraps.
+ *
+ * Each entry point is exactly glabc_key_counts / glabc_histogram / glabc_histogram2d on the history [1][dim][stride] with
+ * n_chains = n, but that a draw ADDS m where the twin adds 1: the same key, levels, prefix rules, bin arithmetic and slot layouts
+ * (counts[(j * n_prefixes + s) << digit_bits | digit]; counts[j * (n_bins + 3) + slot]; counts[p * (n_bins^2 + 2) + slot]), the same
+ * host arrays (prefixes, lo, hi, pairs) and device arrays (x, w, counts), the same limits, and "the call ADDS, the caller zeroes".
+ * With every weight 1.0 and scale 1.0 they return the twins' counts.
+ *
+ * Refusals: the twin's, in the twin's order (w is one of its pointers: NULL is GLABC_ERR_NULL), with GLABC_ERR_ARG also for n < 0
+ * or n > GLABC_MAX_WEIGHTED_DRAWS, stride < n, and a scale that is not finite or not > 0.  A refused call launches nothing and
+ * writes nothing.  n == 0 returns GLABC_OK and writes nothing.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no struct
+ * changes. */
+#define GLABC_MAX_WEIGHTED_DRAWS 2147483648ll
+int glabc_weighted_key_counts(const float* x, int64_t stride, int32_t dim, const float* w, int64_t n, double scale, int32_t level,
+                              int32_t n_prefixes, const uint32_t* prefixes, uint64_t* counts, void* stream);
+int glabc_weighted_histogram(const float* x, int64_t stride, int32_t dim, const float* w, int64_t n, double scale, int32_t n_bins,
+                             const double* lo, const double* hi, uint64_t* counts, void* stream);
+int glabc_weighted_histogram2d(const float* x, int64_t stride, int32_t dim, const float* w, int64_t n, double scale, int32_t n_pairs,
+                               const int32_t* pairs, int32_t n_bins, const double* lo, const double* hi, uint64_t* counts, void* stream);
+
 /* AGLMCMC.py:199-204 (and :104-109): weights of a proposal pool from its stored discrepancies,
  * w[r] = exp((prior(theta_r) + calculate_log_kernel_dis(dis_r)) - log_q[r]), NaN -> 0.  The threshold is the one in
  * model->kern_* (the caller passes a copy of its descriptor with the annealed eps_hat, Mixture.py:47-53).
