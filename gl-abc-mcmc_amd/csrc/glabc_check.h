@@ -505,6 +505,30 @@ inline int check_smc_draws(const glabc_model* m, const glabc_kde* pop, int64_t r
     return check_abc_range(row0, ids, n, stride);
 }
 
+// ---- the lower Cholesky factor of a full-covariance perturbation (glabc_kde_sample_full, glabc_smc_draws_full and its run-time
+// compiled twin): a HOST array of dim (dim + 1) / 2 floats packed row-major, every entry finite, the diagonal positive.  `dim` has
+// passed the population's checks
+inline int check_chol(const float* chol, int32_t dim)
+{
+    if (!chol) return GLABC_ERR_NULL;
+    for (int d = 0, i = 0; d < dim; ++d)
+        for (int e = 0; e <= d; ++e, ++i)
+            if (!std::isfinite(chol[i]) || (e == d && !(chol[i] > 0.0f))) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
+// ---- glabc_smc_draws_full: check_smc_draws with the factor between the population and the range of draws
+inline int check_smc_draws_full(const glabc_model* m, const glabc_kde* pop, const float* chol, int64_t row0, const int64_t* ids, int64_t n,
+                                int64_t stride, const float* theta_out, const float* y_out, const float* dis_out,
+                                const float* log_prior_out, const uint8_t* accept_out)
+{
+    if (!m || !pop || (!theta_out && !y_out && !dis_out && !log_prior_out && !accept_out)) return GLABC_ERR_NULL;
+    if (int e = check_abc_model(m)) return e;
+    if (int e = check_draw_population(pop, m->theta_dim)) return e;
+    if (int e = check_chol(chol, m->theta_dim)) return e;
+    return check_abc_range(row0, ids, n, stride);
+}
+
 // ---- glabc_rtc_steps: a launch of the run-time compiled program of shape `p` -------------------------------------------------
 inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_dist* local, const glabc_dist* global, const glabc_chains* c,
                          const glabc_run* r)
@@ -569,7 +593,7 @@ inline int check_rtc_mix_run(const RtcShape& p, bool mix_program, const glabc_mo
 // refused as glabc_smc_draws refuses it (check_draw_population), between the Model and the range of draws; the prior is
 // check_draw_prior's, the range check_abc_range's.  The order is the contract (include/glabc.h); the entry point has refused a NULL program before.
 inline int check_rtc_draws(const RtcShape& p, bool draws_program, const glabc_model* m, bool smc, const glabc_kde* pop, bool any_output,
-                           int64_t row0, const int64_t* ids, int64_t n, int64_t stride)
+                           int64_t row0, const int64_t* ids, int64_t n, int64_t stride, bool full = false, const float* chol = nullptr)
 {
     if (!m || !any_output) return GLABC_ERR_NULL;
     if (m->sim_kind != GLABC_SIM_USER) return GLABC_ERR_KIND;
@@ -578,6 +602,8 @@ inline int check_rtc_draws(const RtcShape& p, bool draws_program, const glabc_mo
     if (int e = check_draw_prior(m)) return e;
     if (smc)
         if (int e = check_draw_population(pop, m->theta_dim)) return e;
+    if (full)                                                     // glabc_rtc_smc_draws_full: the factor, as glabc_smc_draws_full refuses it
+        if (int e = check_chol(chol, m->theta_dim)) return e;
     return check_abc_range(row0, ids, n, stride);
 }
 

@@ -27,6 +27,7 @@ struct DrawsCall {
     float* dis;
     float* log_prior;                                // smc_draws_kernel only
     uint8_t* accept;
+    const float* chol;                               // smc_draws_kernel<.., true> only: the packed lower factor, a HOST array; else null
 };
 
 // The Model block of a kernel that makes draws: no chains, no proposals, no run
@@ -63,15 +64,30 @@ inline AbcArgs<D, YD> pack_abc_args(const DrawsCall& c)
     return a;
 }
 
-template <int D, int YD>
-inline SmcArgs<D, YD> pack_smc_args(const DrawsCall& c)
+// The population's part of SmcArgs / SmcFullArgs: the same fields under the same names
+template <int D, int YD, class Args>
+inline Args pack_smc_block(const DrawsCall& c)
 {
-    SmcArgs<D, YD> a;
+    Args a;
     std::memset(&a, 0, sizeof a);
     pack_draw_common<D, YD>(c, &a.s, &a.d);
     a.x = c.pop->x, a.cum_q = c.pop->cum_q, a.S = c.pop->n_samples;
     for (int d = 0; d < D; ++d) a.bw[d] = c.pop->bandwidth[d];
     a.log_prior = c.log_prior;
+    return a;
+}
+
+template <int D, int YD>
+inline SmcArgs<D, YD> pack_smc_args(const DrawsCall& c)
+{
+    return pack_smc_block<D, YD, SmcArgs<D, YD>>(c);
+}
+
+template <int D, int YD>
+inline SmcFullArgs<D, YD> pack_smc_full_args(const DrawsCall& c)
+{
+    SmcFullArgs<D, YD> a = pack_smc_block<D, YD, SmcFullArgs<D, YD>>(c);
+    for (int i = 0; i < D * (D + 1) / 2; ++i) a.chol[i] = c.chol[i];
     return a;
 }
 

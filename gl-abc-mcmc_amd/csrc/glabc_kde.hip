@@ -215,6 +215,27 @@ __global__ void __launch_bounds__(256) kde_sample_kernel(const KdeArgs<D> a)
     for (int d = 0; d < D; ++d) a.out[d * a.n_points + r] = z[d];
 }
 
+// glabc_kde_sample_full: the same row under a full-covariance kernel (glabc_kde_draw.h kde_draw_row<D, true>), the row-wise twin of
+// glabc_smc_draws_full's theta.  `bw` of the block is not read
+template <int D>
+struct KdeFullArgs {
+    KdeArgs<D> k;
+    float chol[D * (D + 1) / 2];
+};
+
+template <int D>
+__global__ void __launch_bounds__(256) kde_sample_full_kernel(const KdeFullArgs<D> f)
+{
+    const KdeArgs<D>& a = f.k;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.n_points) return;
+    float z[D];
+    kde_draw_row<D, true>(a.x, a.cum_q, a.n_samples, a.bw, (uint64_t)(a.row0 + r), a.seed_lo, a.seed_hi, z,
+                          [&f]() -> const float* { return f.chol; });
+#pragma unroll
+    for (int d = 0; d < D; ++d) a.out[d * a.n_points + r] = z[d];
+}
+
 template <int D>
 KdeArgs<D> kde_pack(const glabc_kde* k)
 {
@@ -315,6 +336,30 @@ __attribute__((visibility("default"))) int glabc_kde_sample(const glabc_kde* kde
         a.n_points = n; a.out = out; a.row0 = row0;
         a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
         hipLaunchKernelGGL((kde_sample_kernel<D>), grid, block, 0, s, a);
+        return launch_status();
+    });
+}
+
+__attribute__((visibility("default"))) int glabc_kde_sample_full(const glabc_kde* kde, const float* chol, int64_t n, uint64_t seed,
+                                                                 int64_t row0, float* out, void* stream)
+{
+    int rc = kde_check(kde);
+    if (rc) return rc;
+    if ((rc = check_chol(chol, kde->dim))) return rc;
+    if (n < 0 || row0 < 0) return GLABC_ERR_ARG;
+    if (n == 0) return GLABC_OK;
+    if (!out || !kde->cum_q) return GLABC_ERR_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(grid_for(n, 256)), block(256);
+    return dispatch_range<1, 8>(kde->dim, GLABC_ERR_DIM, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        KdeFullArgs<D> f;
+        std::memset(&f, 0, sizeof f);
+        f.k = kde_pack<D>(kde);
+        f.k.n_points = n; f.k.out = out; f.k.row0 = row0;
+        f.k.seed_lo = (uint32_t)seed; f.k.seed_hi = (uint32_t)(seed >> 32);
+        for (int i = 0; i < D * (D + 1) / 2; ++i) f.chol[i] = chol[i];
+        hipLaunchKernelGGL((kde_sample_full_kernel<D>), grid, block, 0, s, f);
         return launch_status();
     });
 }

@@ -1,9 +1,9 @@
 // glabc_rtc_draws_kernels.h -- which kernels a run-time compiled DRAWS program (glabc_rtc_compile_draws, glabc_rtc.hip) holds, as a
-// pure function of its shape: abc_draws_kernel (glabc_abc.h) and smc_draws_kernel (glabc_smc.h) around the user's source, and the two
-// row kernels every program holds.  No sampler kernel.  The pair of glabc_rtc_kernels.h / glabc_rtc_mix_kernels.h for these programs:
+// pure function of its shape: abc_draws_kernel (glabc_abc.h), smc_draws_kernel and its FULL twin (glabc_smc.h) around the
+// user's source, and the two row kernels every program holds.  No sampler kernel.  The pair of glabc_rtc_kernels.h / glabc_rtc_mix_kernels.h for these programs:
 // rtc_draws_kernels says for every slot whether the shape has it, whether its absence is an error, its name expression and its
 // #define; rtc_draws_defines writes the translation unit's #define block.  The entry point names the kernel (glabc_rtc_abc_draws /
-// glabc_rtc_smc_draws): no launch plan maps to these slots.  Host only, no HIP, never handed to hiprtc.
+// glabc_rtc_smc_draws / glabc_rtc_smc_draws_full): no launch plan maps to these slots.  Host only, no HIP, never handed to hiprtc.
 #pragma once
 
 #include <cstdio>
@@ -18,6 +18,7 @@ enum RtcDrawsSlot {
     RTC_DRAWS_ABC,                                         // abc_draws_kernel<D, YD>
     RTC_DRAWS_SMC,                                         // smc_draws_kernel<D, YD>
     RTC_DRAWS_SIMULATE_ROWS, RTC_DRAWS_MODEL_ROWS,         // the extern "C" row kernels
+    RTC_DRAWS_SMC_FULL,                                    // smc_draws_kernel<D, YD, true> (glabc_rtc_smc_draws_full)
     RTC_DRAWS_SLOTS
 };
 
@@ -39,6 +40,7 @@ inline RtcDrawsKernels rtc_draws_kernels(const RtcShape& s)
     t.k[RTC_DRAWS_MODEL_ROWS] = RtcKernel{true, true, false, nullptr, "glabc_rtc_model_rows_kernel"};
     add(RTC_DRAWS_ABC, "glabc::abc_draws_kernel<%d, %d>", s.theta_dim, s.y_dim);
     add(RTC_DRAWS_SMC, "glabc::smc_draws_kernel<%d, %d>", s.theta_dim, s.y_dim);
+    add(RTC_DRAWS_SMC_FULL, "glabc::smc_draws_kernel<%d, %d, true>", s.theta_dim, s.y_dim);
     return t;
 }
 

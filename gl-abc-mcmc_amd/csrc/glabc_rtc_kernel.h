@@ -24,8 +24,8 @@
 // above: sampler_kernel<.., 1, VAR_MIX, 0> (one lane per chain whatever GLABC_RTC_L is: chain_step asserts it), or, with
 // GLABC_RTC_WIDE, wide_kernel<.., false, true> at the four lane counts.  Their argument block is a MixStepArgs (glabc_device.h).
 //
-// GLABC_RTC_DRAWS (glabc_rtc_compile_draws) instantiates no sampler at all: abc_draws_kernel (glabc_abc.h) and smc_draws_kernel
-// (glabc_smc.h), the templates glabc_abc_draws and glabc_smc_draws are instantiated from, with the user's function where the built-in
+// GLABC_RTC_DRAWS (glabc_rtc_compile_draws) instantiates no sampler at all: abc_draws_kernel (glabc_abc.h), smc_draws_kernel and
+// smc_draws_kernel<.., true> (glabc_smc.h), the templates glabc_abc_draws, glabc_smc_draws and glabc_smc_draws_full are instantiated from, with the user's function where the built-in
 // simulators are.  GLABC_RTC_ALGO / _N / _L are not defined for such a program.
 //
 // GLABC_RTC_PREDICTIVE (glabc_rtc_compile_predictive) instantiates predictive_kernel (glabc_predictive.h), the template
@@ -48,6 +48,7 @@ template __global__ void predictive_kernel<GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_
 namespace glabc {
 template __global__ void abc_draws_kernel<GLABC_RTC_D, GLABC_RTC_YD>(const AbcArgs<GLABC_RTC_D, GLABC_RTC_YD>);
 template __global__ void smc_draws_kernel<GLABC_RTC_D, GLABC_RTC_YD>(const SmcArgs<GLABC_RTC_D, GLABC_RTC_YD>);
+template __global__ void smc_draws_kernel<GLABC_RTC_D, GLABC_RTC_YD, true>(const SmcFullArgs<GLABC_RTC_D, GLABC_RTC_YD>);
 #elif defined(GLABC_RTC_WIDE) && defined(GLABC_RTC_WITH_MIX)
 }  // namespace glabc
 #include "glabc_wide.h"

@@ -1,6 +1,9 @@
 // glabc_smc.h -- smc_draws_kernel<D, YD>: the kernel of the ABC-SMC proposals, as glabc_smc.hip instantiates it for the built-in
 // simulators (glabc_smc_draws) and as hiprtc instantiates it around a user's simulator (glabc_rtc_compile_draws, glabc_rtc_kernel.h).
 // include/glabc.h holds the specification of a draw.  No host includes: the header is handed to hiprtc as text.
+// smc_draws_kernel<D, YD, true> is the same text under a full-covariance perturbation kernel (glabc_smc_draws_full): theta through
+// kde_draw_row<D, true>, the Cholesky factor behind the block (SmcFullArgs) and read after the ancestor search
+// (profiles/smc_full_kernel_resources.txt).  The diagonal instantiations compile to the instructions they had before the flag.
 //
 // smc_draws_kernel<D, YD> is abc_draws_kernel (glabc_abc.h) with theta from a fitted population instead of the prior, the prior's
 // log-density as a fifth output and the distance +inf where that is -inf; the rest is glabc_draw.h's, which both call.  One lane owns
@@ -33,15 +36,33 @@ struct SmcArgs {
     float* log_prior;
 };
 
+// The argument of smc_draws_kernel<D, YD, true> (glabc_smc_draws_full): the same fields under the same names -- `bw` is not read --
+// and the lower Cholesky factor of the perturbation's covariance behind them, packed row-major (glabc_kde_draw.h)
+template <int D, int YD>
+struct SmcFullArgs {
+    StepArgs<D, YD> s;
+    const float* x;
+    const int64_t* cum_q;
+    int64_t S;
+    float bw[D];
+    DrawArgs d;
+    float* log_prior;
+    float chol[D * (D + 1) / 2];
+};
+
+template <int D, int YD, bool FULL>
+struct SmcKernelArgs { using type = SmcArgs<D, YD>; };
+template <int D, int YD>
+struct SmcKernelArgs<D, YD, true> { using type = SmcFullArgs<D, YD>; };
+
 // The Model block of the kernel's argument, read where it is used.  The compiler loads a by-value argument in the entry block and sinks
 // the loads no further than the head of the ancestor search's loop: at D = 7 and 8 the prior, the noise and y_obs then live in scalar
 // registers across the loop, past the 102 a wavefront has (8 spilled, seven wavefronts per SIMD).  Behind a pointer the compiler
 // cannot see through, the loads are emitted after the loop.  `s` is the first member of the only argument: offset 0 of the segment
-template <int D, int YD>
-GLABC_DEV const StepArgs<D, YD>& model_after_search(const SmcArgs<D, YD>& a)
+template <int D, int YD, class Args>
+GLABC_DEV const StepArgs<D, YD>& model_after_search(const Args& a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using Args = SmcArgs<D, YD>;
     static_assert(__builtin_offsetof(Args, s) == 0, "the Model block leads the argument");
     auto p = __builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
@@ -51,8 +72,26 @@ GLABC_DEV const StepArgs<D, YD>& model_after_search(const SmcArgs<D, YD>& a)
 #endif
 }
 
+// L in the same way: up to 36 more scalars at D = 8, which must not live across the search either.  kde_draw_row asks for it after
+// its loop
 template <int D, int YD>
-__global__ void __launch_bounds__(DRAW_BLOCK) smc_draws_kernel(const SmcArgs<D, YD> a)
+struct CholAfterSearch {
+    const SmcFullArgs<D, YD>& a;
+    __device__ __forceinline__ const float* operator()() const
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        auto p = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(p));
+        return ((const SmcFullArgs<D, YD>*)p)->chol;
+#else
+        return a.chol;
+#endif
+    }
+};
+
+// FULL: glabc_smc_draws_full, the full-covariance perturbation of include/glabc.h; one text for both
+template <int D, int YD, bool FULL = false>
+__global__ void __launch_bounds__(DRAW_BLOCK) smc_draws_kernel(const typename SmcKernelArgs<D, YD, FULL>::type a)
 {
     const int64_t r = draw_row(a.d);
     if (r >= a.d.n) return;
@@ -60,10 +99,11 @@ __global__ void __launch_bounds__(DRAW_BLOCK) smc_draws_kernel(const SmcArgs<D, 
 
     // theta: row id of glabc_kde_sample(population), through the function its kernel draws with (glabc_kde_draw.h)
     float theta[D], y[YD];
-    kde_draw_row<D>(a.x, a.cum_q, a.S, a.bw, id, a.d.theta_lo, a.d.theta_hi, theta);
+    if constexpr (FULL) kde_draw_row<D, true>(a.x, a.cum_q, a.S, a.bw, id, a.d.theta_lo, a.d.theta_hi, theta, CholAfterSearch<D, YD>{a});
+    else kde_draw_row<D>(a.x, a.cum_q, a.S, a.bw, id, a.d.theta_lo, a.d.theta_hi, theta);
     draw_store<D>(a.d.theta, a.d, r, theta);
     if (!a.d.y && !a.d.dis && !a.log_prior && !a.d.accept) return;
-    const StepArgs<D, YD>& m = model_after_search(a);
+    const StepArgs<D, YD>& m = model_after_search<D, YD>(a);
 
     // the prior's log-density: glabc_model_prior_log_prob; the distance and the acceptance need to know where it is -inf
     float lp = 0.0f;

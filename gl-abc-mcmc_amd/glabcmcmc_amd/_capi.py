@@ -346,6 +346,12 @@ ENTRY_POINTS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_rtc_smc_draws": (C.c_int, [C.c_void_p, _P(Model), _P(Kde), C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the full-covariance perturbation kernel: `chol` (second / third / fourth argument) is a HOST array of dim (dim + 1) / 2 floats
+    "glabc_kde_sample_full": (C.c_int, [_P(Kde), C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "glabc_smc_draws_full": (C.c_int, [_P(Model), _P(Kde), C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glabc_rtc_smc_draws_full": (C.c_int, [C.c_void_p, _P(Model), _P(Kde), C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_rtc_compile_predictive": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),
     "glabc_rtc_predictive_draws": (C.c_int, [C.c_void_p, _P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint64,
                                              C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -247,7 +247,7 @@ class CompiledModel:
                 "simulator source)" % (algo, batch_size, bad, n_chains, steps))
         return True
 
-    # ---- the draws program: abc_draws_kernel and smc_draws_kernel around the source (rejection.py, smc.py) --------------------
+    # ---- the draws program: abc_draws_kernel, smc_draws_kernel and its full-covariance twin around the source (rejection.py, smc.py) --------------------
     DRAWS = "draws"
 
     def draws_refusal(self):
@@ -292,9 +292,9 @@ class CompiledModel:
                 raise
         return self._programs[key]
 
-    def composed_draws(self, handle, desc, seed, row0, n, population=None):
+    def composed_draws(self, handle, desc, seed, row0, n, population=None, chol=None):
         """Draws row0 .. row0 + n - 1 as include/glabc.h specifies them, from the entry points a draw is composed of: theta from
-        glabc_dist_forward of the prior (glabc_kde_sample of `population`), eps from glabc_dist_forward of a standard DiagGaussian
+        glabc_dist_forward of the prior (glabc_kde_sample of `population`; with the packed factor `chol`: glabc_kde_sample_full), eps from glabc_dist_forward of a standard DiagGaussian
         under seed ^ GLABC_ABC_NOISE_KEY, y from glabc_rtc_simulate, the distance from glabc_rtc_model_rows / glabc_model_discrepancy,
         log_prior from glabc_model_prior_log_prob (+inf rule applied) -> {name: device tensor}, theta (n, D) and y (n, YD)"""
         lib, dev = _capi.lib(), engine.require_device(None)
@@ -304,8 +304,11 @@ class CompiledModel:
         with torch.cuda.device(dev):
             if population is None:
                 _capi.check(lib.glabc_dist_forward(C.byref(desc.prior), n, seed, row0, z.data_ptr(), lq.data_ptr(), stream), "glabc_dist_forward")
-            else:
+            elif chol is None:
                 _capi.check(lib.glabc_kde_sample(C.byref(population.descriptor()), n, seed, row0, z.data_ptr(), stream), "glabc_kde_sample")
+            else:
+                _capi.check(lib.glabc_kde_sample_full(C.byref(population.descriptor()), chol, n, seed, row0, z.data_ptr(), stream),
+                            "glabc_kde_sample_full")
             theta = z.t().contiguous()
             e = torch.empty(self.noise_dim, n, dtype=torch.float32, device=dev)
             _capi.check(lib.glabc_dist_forward(C.byref(desc.noise), n, seed ^ _capi.ABC_NOISE_KEY, row0, e.data_ptr(), lq.data_ptr(), stream),
@@ -355,9 +358,10 @@ class CompiledModel:
         return (u < p.cpu().numpy()).astype(np.uint8)
 
     def self_check_draws(self, handle, seed=20240229):
-        """The two draw kernels of a freshly compiled draws program against the composition that specifies a draw (composed_draws),
+        """The three draw kernels of a freshly compiled draws program against the composition that specifies a draw (composed_draws),
         bit for bit: 320 draws in three runs of consecutive ids -- from 0, across 2^32 and above 2^40 --, listed out of order; theta,
-        y, distance (and log_prior) together, then each output alone; the SMC kernel from a population of 48 prior draws.  The
+        y, distance (and log_prior) together, then each output alone; the SMC kernel from a population of 48 prior draws, and its full-covariance twin from the same
+        population with a factor that is not diagonal (composition: glabc_kde_sample_full -> glabc_rtc_simulate -> ...).  The
         acceptance byte is compared with composed_accept where the kernel is the descriptor's; a user kernel (GLABC_USER_KERNEL) has
         no entry point that evaluates it at a given distance, so its byte is only held to what must be: the same alone as with the
         other outputs, and 0 where the distance is NaN or +inf.  Runs once per Model (a few ms); GLABC_RTC_SELF_CHECK=0 skips it."""
@@ -376,8 +380,12 @@ class CompiledModel:
         with torch.cuda.device(dev):
             _capi.check(lib.glabc_dist_forward(C.byref(desc.prior), 48, seed + 1, 0, z.data_ptr(), lq.data_ptr(), stream), "glabc_dist_forward")
         population = KernelDensity("silverman", device=dev).fit(z.t().contiguous())
+        # the factor of the full-covariance kernel: the bandwidths on the diagonal, +-0.3 of them below it
+        D = self.theta_dim
+        bw = [float(v) for v in population.bandwidth.cpu()]
+        chol = (C.c_float * (D * (D + 1) // 2))(*[bw[d] * (1.0 if e == d else 0.3 * (-1.0) ** (d + e)) for d in range(D) for e in range(d + 1)])
 
-        def fused(pop, want):
+        def fused(pop, want, chol=None):
             shapes = {"theta": (self.theta_dim, n), "y": (self.y_dim, n), "distance": (n,), "log_prior": (n,), "accept": (n,)}
             out = {k: torch.empty(shapes[k], dtype=torch.uint8 if k == "accept" else torch.float32, device=dev) for k in want}
             ptr = lambda k: out[k].data_ptr() if k in out else None          # noqa: E731
@@ -385,10 +393,14 @@ class CompiledModel:
                 if pop is None:
                     _capi.check(lib.glabc_rtc_abc_draws(handle, C.byref(desc), seed, 0, ids_dev.data_ptr(), n, n, ptr("theta"), ptr("y"),
                                                         ptr("distance"), ptr("accept"), stream), "glabc_rtc_abc_draws")
-                else:
+                elif chol is None:
                     _capi.check(lib.glabc_rtc_smc_draws(handle, C.byref(desc), C.byref(pop.descriptor()), seed, 0, ids_dev.data_ptr(), n, n,
                                                         ptr("theta"), ptr("y"), ptr("distance"), ptr("log_prior"), ptr("accept"), stream),
                                 "glabc_rtc_smc_draws")
+                else:
+                    _capi.check(lib.glabc_rtc_smc_draws_full(handle, C.byref(desc), C.byref(pop.descriptor()), chol, seed, 0, ids_dev.data_ptr(),
+                                                             n, n, ptr("theta"), ptr("y"), ptr("distance"), ptr("log_prior"), ptr("accept"),
+                                                             stream), "glabc_rtc_smc_draws_full")
             return {k: (v.t().contiguous() if k in ("theta", "y") else v).cpu().numpy() for k, v in out.items()}
 
         def refuse(kernel, name, detail=""):
@@ -396,11 +408,12 @@ class CompiledModel:
                 "the run-time compiled %s disagrees with the composition of entry points that specifies a draw in `%s`%s: refusing to "
                 "draw with it (use path='generic', and please report the simulator source)" % (kernel, name, detail))
 
-        for pop, kernel in ((None, "abc_draws_kernel"), (population, "smc_draws_kernel")):
+        for pop, L, kernel in ((None, None, "abc_draws_kernel"), (population, None, "smc_draws_kernel"),
+                               (population, chol, "smc_draws_kernel (full covariance)")):
             names = ("theta", "y", "distance") + (("log_prior",) if pop is not None else ())
-            parts = [self.composed_draws(handle, desc, seed, a, k, pop) for a, k in runs]
+            parts = [self.composed_draws(handle, desc, seed, a, k, pop, L) for a, k in runs]
             want = {k: torch.cat([p[k] for p in parts]).cpu().numpy()[order] for k in names}
-            got = fused(pop, names + ("accept",))
+            got = fused(pop, names + ("accept",), L)
             for k in names:
                 if not np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)):
                     refuse(kernel, k, " (%d of %d draws)" % (int((got[k].view(np.uint32) != want[k].view(np.uint32)).reshape(n, -1).any(axis=1).sum()), n))
@@ -410,7 +423,7 @@ class CompiledModel:
             elif not np.array_equal(got["accept"], self.composed_accept(desc, seed, ids[order], want["distance"])):
                 refuse(kernel, "accept")
             for k in names + ("accept",):                               # each output alone: the scalar branches around the NULL ones
-                alone = fused(pop, (k,))[k]
+                alone = fused(pop, (k,), L)[k]
                 if not np.array_equal(alone.view(np.uint8), got[k].view(np.uint8)):
                     refuse(kernel, k, " asked for alone")
         return True

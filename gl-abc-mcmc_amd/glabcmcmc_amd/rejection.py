@@ -98,7 +98,8 @@ def accepted(ABCset, epsilon=None):
 
 class _Entry:
     """The fused draws of one Model: its glabc_model and the entry points that take it -- glabc_abc_draws / glabc_smc_draws for the
-    built-in simulators, glabc_rtc_abc_draws / glabc_rtc_smc_draws with the draws program of a CompiledModel.  ``abc`` and ``smc`` take
+    built-in simulators, glabc_rtc_abc_draws / glabc_rtc_smc_draws with the draws program of a CompiledModel.  ``abc`` and ``smc`` (and
+    ``smc_full``: glabc_smc_draws_full / glabc_rtc_smc_draws_full) take
     the arguments of the C entry points after the Model (and the population), and raise on a status other than GLABC_OK."""
 
     def __init__(self, desc, program=None):
@@ -118,6 +119,15 @@ class _Entry:
             _capi.check(lib.glabc_smc_draws(C.byref(self.desc), C.byref(kde_desc), *args), "glabc_smc_draws")
         else:
             _capi.check(lib.glabc_rtc_smc_draws(self.program, C.byref(self.desc), C.byref(kde_desc), *args), "glabc_rtc_smc_draws")
+
+    def smc_full(self, kde_desc, chol, *args):
+        """``smc`` under a full-covariance perturbation kernel: `chol` is the packed lower factor, a ctypes array of floats"""
+        lib = _capi.lib()
+        if self.program is None:
+            _capi.check(lib.glabc_smc_draws_full(C.byref(self.desc), C.byref(kde_desc), chol, *args), "glabc_smc_draws_full")
+        else:
+            _capi.check(lib.glabc_rtc_smc_draws_full(self.program, C.byref(self.desc), C.byref(kde_desc), chol, *args),
+                        "glabc_rtc_smc_draws_full")
 
 
 def _path(ABCset, path, epsilon):

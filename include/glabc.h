@@ -990,6 +990,37 @@ int glabc_smc_draws(const glabc_model* model, const glabc_kde* population, uint6
                     int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out, float* log_prior_out,
                     uint8_t* accept_out, void* stream);
 
+/* ---- The same proposals under a full-covariance perturbation kernel (Filippi et al. 2013; Beaumont et al. 2009 in its multivariate
+ * form): theta = x_j + L nrm, L the lower Cholesky factor of the kernel's covariance (glabcmcmc_amd/smc.py: a multiple of the weighted
+ * population covariance).  `chol` is a HOST array of dim (dim + 1) / 2 float32 packed row-major: chol[d (d + 1) / 2 + e] = L[d][e],
+ * e <= d; it travels in the kernel's argument block.
+ *
+ * Specification of theta for draw `id` -- it departs from glabc_kde_sample's row (above) in its last line only:
+ *     the Philox blocks, the float64 uniform u, the ancestor j and the normals nrm[0 .. dim) are glabc_kde_sample's: no new random
+ *     number is used and no existing draw moves;
+ *     acc = nrm_0 * L[d][0], then acc = acc + nrm_e * L[d][e] for e = 1 .. d ascending, every product and every sum a rounded float32
+ *     operation (no fused multiply-add: -ffp-contract=off is part of the specification, as elsewhere);
+ *     theta_d = x[d * n_samples + j] + acc
+ * so IEEE float32 arithmetic restates it bit for bit, and a diagonal L gives glabc_kde_sample's / glabc_smc_draws' draws with
+ * bandwidth = diag(L) bit for bit (0 * nrm_e = +-0 and +-0 + v = v), but for a coordinate x = -0 of the ancestor whose acc is +0.
+ * The population's bandwidth, sum_log_bw and c_2pi are not read for drawing (they still pass the population's checks: the Python
+ * layer fills bandwidth with the marginal scales sqrt(diag(L L^T))).
+ *
+ * glabc_kde_sample_full is glabc_kde_sample with that row: out dimension-major [dim][n].  Refusals, in this order: those of
+ * glabc_kde_sample on kde; a NULL chol GLABC_ERR_NULL; an entry of chol that is not finite or a diagonal entry <= 0 GLABC_ERR_ARG;
+ * then n < 0 or row0 < 0 GLABC_ERR_ARG; n == 0 returns GLABC_OK; a NULL out or cum_q GLABC_ERR_NULL.
+ *
+ * glabc_smc_draws_full is glabc_smc_draws with theta = row id of glabc_kde_sample_full(population, chol, ., seed, .); log_prior, y,
+ * dis and accept, the ids, layouts and NULL outputs are glabc_smc_draws'.  Its refusals are glabc_smc_draws', in that order, with the
+ * two of chol (NULL: GLABC_ERR_NULL; not finite, or a diagonal entry <= 0: GLABC_ERR_ARG) after population->dim != theta_dim and before
+ * the range of draws.  A refused call launches nothing and writes nothing.  glabc_rtc_smc_draws_full is glabc_rtc_smc_draws in the
+ * same way: the same kernel (csrc/glabc_smc.h smc_draws_kernel<D, YD, true>) in the draws program of glabc_rtc_compile_draws, chol refused at
+ * the same place.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no struct changes and no existing draw moves. */
+int glabc_kde_sample_full(const glabc_kde* kde, const float* chol, int64_t n, uint64_t seed, int64_t row0, float* out, void* stream);
+int glabc_smc_draws_full(const glabc_model* model, const glabc_kde* population, const float* chol, uint64_t seed, int64_t row0,
+                         const int64_t* ids, int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out,
+                         float* log_prior_out, uint8_t* accept_out, void* stream);
+
 /* ---- The two draw kernels around a USER simulator (csrc/glabc_rtc.hip): glabc_abc_draws and glabc_smc_draws for GLABC_SIM_USER Models.
  * glabc_rtc_compile_draws compiles (hiprtc, gfx950) the templates those two entry points are instantiated from -- abc_draws_kernel
  * (csrc/glabc_abc.h) and smc_draws_kernel (csrc/glabc_smc.h) -- around `simulator_source` (the source of glabc_rtc_compile, with its
@@ -1037,6 +1068,10 @@ int glabc_rtc_abc_draws(const glabc_rtc_program* program, const glabc_model* mod
 int glabc_rtc_smc_draws(const glabc_rtc_program* program, const glabc_model* model, const glabc_kde* population, uint64_t seed,
                         int64_t row0, const int64_t* ids, int64_t n, int64_t stride, float* theta_out, float* y_out, float* dis_out,
                         float* log_prior_out, uint8_t* accept_out, void* stream);
+/* glabc_rtc_smc_draws under a full-covariance perturbation kernel: see glabc_smc_draws_full */
+int glabc_rtc_smc_draws_full(const glabc_rtc_program* program, const glabc_model* model, const glabc_kde* population, const float* chol,
+                             uint64_t seed, int64_t row0, const int64_t* ids, int64_t n, int64_t stride, float* theta_out, float* y_out,
+                             float* dis_out, float* log_prior_out, uint8_t* accept_out, void* stream);
 
 /* ---- The posterior predictive kernel around a USER simulator (csrc/glabc_rtc.hip): glabc_predictive_draws and glabc_predictive_counts
  * for GLABC_SIM_USER Models.  glabc_rtc_compile_predictive compiles (hiprtc, gfx950) the template those two entry points are
