@@ -472,6 +472,22 @@ inline int check_predictive_counts(const glabc_model* m, const float* history, i
     return GLABC_OK;
 }
 
+// ---- glabc_weighted_predictive_counts (and, with PredModelCheck{true}, its run-time compiled twin): check_predictive_counts on the
+// one-row history [1][theta_dim][stride] of n draws with id_step = n -- so n < 0, stride < n, id0 < 0 and a last id id0 + n - 1 past
+// int64 are its own -- with a null weight array a null pointer like the others; then what the weights add (check_weight_scale) and
+// the smaller limit on the bins, looked at where the twin looks at its own
+inline int check_weighted_predictive_counts(const glabc_model* m, const float* x, int64_t stride, int32_t theta_dim, const float* w, int64_t n,
+                                            double scale, int64_t id0, int32_t n_bins, const double* lo, const double* hi,
+                                            const float* threshold, const uint64_t* counts, const uint64_t* tails, const uint32_t* extremes,
+                                            const PredModelCheck& model_check = PredModelCheck())
+{
+    if (!w) return GLABC_ERR_NULL;
+    if (int e = check_predictive_counts(m, x, 1, theta_dim, n, stride, id0, n, n_bins, lo, hi, threshold, counts, tails, extremes, model_check))
+        return e;
+    if (counts && n_bins > GLABC_MAX_WEIGHTED_PREDICTIVE_BINS) return GLABC_ERR_ARG;
+    return check_weight_scale(n, scale);
+}
+
 // ---- glabc_kde: what every entry point that reads a fitted KernelDensity asks of its descriptor (cum_q is glabc_kde_sample's and
 // glabc_smc_draws' alone and they ask for it themselves)
 inline int kde_check(const glabc_kde* k)

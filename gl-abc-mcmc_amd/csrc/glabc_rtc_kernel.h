@@ -30,13 +30,23 @@
 //
 // GLABC_RTC_PREDICTIVE (glabc_rtc_compile_predictive) instantiates predictive_kernel (glabc_predictive.h), the template
 // glabc_predictive_draws and glabc_predictive_counts are instantiated from, at GLABC_RTC_PRED_ROWS rows per item, and nothing else.
+//
+// GLABC_RTC_WEIGHTED_PREDICTIVE (glabc_rtc_compile_weighted_predictive) instantiates weighted_predictive_kernel
+// (glabc_weighted_predictive.h), the template glabc_weighted_predictive_counts is instantiated from, at GLABC_RTC_WPRED_SEGMENTS
+// segments per item, and nothing else.
 #pragma once
 
 #include "glabc_sampler.h"
 
 namespace glabc {
 
-#if defined(GLABC_RTC_PREDICTIVE)
+#if defined(GLABC_RTC_WEIGHTED_PREDICTIVE)
+}  // namespace glabc
+#include "glabc_weighted_predictive.h"
+namespace glabc {
+template __global__ void weighted_predictive_kernel<GLABC_RTC_D, GLABC_RTC_YD, GLABC_RTC_WPRED_SEGMENTS>(
+    const WeightedPredArgs<GLABC_RTC_D, GLABC_RTC_YD>);
+#elif defined(GLABC_RTC_PREDICTIVE)
 }  // namespace glabc
 #include "glabc_predictive.h"
 namespace glabc {

@@ -2,14 +2,15 @@
 // values (JointSlots) adds to, or none.  glabc_quant.hip and glabc_joint.hip count one per draw of a chain-major history with them,
 // glabc_weighted.hip a draw's quantised weight: one text, so the key, the levels, the prefix rules, the bin arithmetic
 // (glabc_history.h) and the slot layouts of the weighted entry points are those of their unweighted twins.  The slot structures
-// travel as kernel arguments; the functions that fill them run on the host.  The quantised weight of include/glabc.h is stated here
-// too, host and device.
+// travel as kernel arguments; the functions that fill them run on the host.  The quantised weight of include/glabc.h comes with
+// glabc_weighted_walk.h, host and device, which a run-time compiled program is given too.
 #pragma once
 
 #include <cstdint>
 
 #include "glabc_check.h"
 #include "glabc_history.h"
+#include "glabc_weighted_walk.h"
 
 namespace glabc {
 
@@ -129,17 +130,6 @@ inline JointSlots joint_slots(int32_t n_pairs, const int32_t* pairs, int32_t n_b
     }
     j.n_bins = n_bins;
     return j;
-}
-
-// ---- the quantised weight of the weighted entry points (include/glabc.h): the multiplicity a draw of float32 weight w counts
-// with.  One rounded product (the objects are built with -ffp-contract=off), ties to even; zero, negative and NaN weights count
-// nothing, and the clamp keeps a multiplicity inside 32 bits so that 2^31 of them cannot wrap a uint64
-__host__ __device__ inline uint64_t weight_multiplicity(float w, double scale)
-{
-    const double v = (double)w * scale;
-    if (!(w > 0.0f)) return 0u;
-    if (v >= 4294967295.0) return 0xFFFFFFFFull;
-    return (uint64_t)(uint32_t)__builtin_rint(v);
 }
 
 }  // namespace glabc

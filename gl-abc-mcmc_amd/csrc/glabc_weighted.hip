@@ -1,12 +1,13 @@
 // glabc_weighted.hip -- integer counts over weighted draws: glabc_weighted_key_counts, glabc_weighted_histogram and
 // glabc_weighted_histogram2d of include/glabc.h, which holds the specification.  Each is its unweighted twin (glabc_quant.hip,
 // glabc_joint.hip) on the one-row history [1][dim][stride], with a draw adding its quantised weight m (weight_multiplicity,
-// glabc_slots.h) where the twin adds 1; the slot functions are the twins' own text (glabc_slots.h), so the key, the levels, the prefix
+// glabc_weighted_walk.h) where the twin adds 1; the slot functions are the twins' own text (glabc_slots.h), so the key, the levels, the prefix
 // rules, the bin arithmetic and the slot layouts cannot differ.
 //
 // weighted_count_kernel<Slots> / weighted_joint_kernel.  Lanes run along the draws and blockIdx.y is the coordinate (the pair).  The
 // draws are cut into items of 64 x WEIGHTED_SEGMENTS consecutive draws, which the 8 wavefronts of the gridDim.x workgroups take
-// round-robin.  Every 64-draw segment of an item, the weights' included, is loaded through load_segment (glabc_history.h) with a
+// round-robin (the walk, the 64-bit table helpers and the quantised weight are glabc_weighted_walk.h's, which
+// glabc_weighted_predictive.h shares).  Every 64-draw segment of an item, the weights' included, is loaded through load_segment (glabc_history.h) with a
 // descriptor over exactly its bytes: a padding column, the floats behind the last draw and -- with no bytes -- a whole segment past
 // the end cannot be read, whatever the base's alignment.  The loads of an item are issued together, and a lane outside its segment
 // adds nothing, whatever the load returned.  A draw of multiplicity 0 is skipped before its value is looked at: a NaN that carries
@@ -30,72 +31,18 @@
 #include "glabc_launch.h"
 #include "glabc_lds_grant.h"
 #include "glabc_slots.h"
+#include "glabc_weighted_walk.h"
 
 namespace glabc {
 
 constexpr int WEIGHTED_SEGMENTS = 4;    // 64-draw segments per item: 8 (one coordinate) or 12 (a pair) loads in flight together
 constexpr int64_t WEIGHTED_ITEM = (int64_t)HISTORY_LANES * WEIGHTED_SEGMENTS;
 
-// ---- the walk over the draws: item i holds draws [i * WEIGHTED_ITEM, min(n, (i + 1) * WEIGHTED_ITEM)).  All wave-uniform
-constexpr int64_t weighted_items(int64_t n) { return (n + WEIGHTED_ITEM - 1) / WEIGHTED_ITEM; }
-
-struct DrawItem {
-    int64_t draw0;
-    int draws;                          // draws inside the item: 1 .. WEIGHTED_ITEM
-    // segment r is loaded with bytes(r) bytes at offset at(r) from the item's first draw: a segment past the end has the item's own
-    // address and no bytes, and only a lane below live(r) may count what it loaded
-    __device__ int live(int r) const
-    {
-        const int left = draws - r * HISTORY_LANES;
-        return left < 0 ? 0 : left < HISTORY_LANES ? left : HISTORY_LANES;
-    }
-    __device__ int bytes(int r) const { return 4 * live(r); }
-    __device__ int64_t at(int r) const { return draw0 + (live(r) ? r * HISTORY_LANES : 0); }
-};
-
-struct DrawWalk {
-    const int64_t n;
-    const int64_t n_items = weighted_items(n);
-    const int64_t n_waves = (int64_t)gridDim.x * HISTORY_WAVES;
-    const int64_t first = (int64_t)blockIdx.x * HISTORY_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.y);          // this wavefront's
-
-    __device__ explicit DrawWalk(int64_t draws) : n(draws) {}
-    __device__ DrawItem item(int64_t i) const
-    {
-        const int64_t draw0 = i * WEIGHTED_ITEM;
-        return DrawItem{draw0, (int)(n - draw0 < WEIGHTED_ITEM ? n - draw0 : WEIGHTED_ITEM)};
-    }
-};
-
-// ---- the table: glabc_history.h's three helpers on 64-bit counters; every store of the kernels below goes through them
-__device__ __forceinline__ void table_zero(unsigned long long* table, int n_slots)
-{
-    const int tid = threadIdx.y * HISTORY_LANES + threadIdx.x;
-    for (int i = tid; i < n_slots; i += HISTORY_LANES * HISTORY_WAVES) table[i] = 0ull;
-    __syncthreads();
-}
-
-// slot < 0: nothing to add.  A caller's slot function returns an index below the n_slots the table was launched with
-__device__ __forceinline__ void lds_add(unsigned long long* table, int slot, unsigned long long m)
-{
-    if (slot >= 0) atomicAdd(&table[slot], m);
-}
-
-__device__ __forceinline__ void table_flush(const unsigned long long* table, int n_slots, unsigned long long* out)
-{
-    __syncthreads();
-    const int tid = threadIdx.y * HISTORY_LANES + threadIdx.x;
-    for (int i = tid; i < n_slots; i += HISTORY_LANES * HISTORY_WAVES) {
-        const unsigned long long c = table[i];
-        if (c) atomicAdd(&out[i], c);
-    }
-}
-
-// the multiplicity lane `lane` of segment r counts with: 0 outside the segment, whatever the load returned
-__device__ __forceinline__ unsigned long long lane_multiplicity(const DrawItem& it, int r, unsigned lane, float w, double scale)
-{
-    return (int)lane < it.live(r) ? (unsigned long long)weight_multiplicity(w, scale) : 0ull;
-}
+// ---- the walk over the draws (glabc_weighted_walk.h) at WEIGHTED_SEGMENTS segments per item; the 64-bit table helpers and
+// lane_multiplicity are that header's too
+constexpr int64_t weighted_items(int64_t n) { return draw_items<WEIGHTED_SEGMENTS>(n); }
+using DrawItem = DrawItemOf<WEIGHTED_SEGMENTS>;
+using DrawWalk = DrawWalkOf<WEIGHTED_SEGMENTS>;
 
 template <class Slots>
 __global__ void __launch_bounds__(HISTORY_LANES* HISTORY_WAVES)

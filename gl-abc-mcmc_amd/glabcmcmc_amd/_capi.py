@@ -368,6 +368,13 @@ ENTRY_POINTS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_weighted_histogram2d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p,
                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glabc_weighted_predictive_counts": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_uint64,
+                                                   C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]),
+    "glabc_rtc_compile_weighted_predictive": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_char_p, C.c_int64]),
+    "glabc_rtc_weighted_predictive_counts": (C.c_int, [C.c_void_p, _P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                       C.c_double, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_selftest_numerics": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "glabc_selftest_sqrt": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "glabc_selftest_rowsum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

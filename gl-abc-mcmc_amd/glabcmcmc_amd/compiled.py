@@ -57,7 +57,10 @@ or Uniform descriptor prior there.
 ``predictive`` runs fused on a ``CompiledModel`` too: ``predictive_program()`` compiles ``predictive_kernel`` of
 ``glabc_predictive_counts`` / ``glabc_predictive_draws`` around the source (``glabc_rtc_compile_predictive``; a program of its own in the
 cache) and checks it, bit for bit, against the composition of entry points that specifies a predictive draw before it is handed
-out.  Any prior will do, a user prior included: theta comes from the history.
+out.  Any prior will do, a user prior included: theta comes from the history.  ``predictive.check_weighted`` has a program of its
+own again: ``weighted_predictive_program()`` compiles ``weighted_predictive_kernel`` of ``glabc_weighted_predictive_counts`` around
+the source (``glabc_rtc_compile_weighted_predictive``) and holds its tables to integer sums of the quantised weights over the draws
+of the predictive program before it is handed out.
 
 Use + - * / fmaf sqrtf fabsf and the ``glabc_*`` functions of include/glabc_numerics.h (``glabc_expf``,
 ``glabc_logf``, ``glabc_sincos2pi`` ...) for results that a CPU build of the same source reproduces bit for bit.
@@ -607,6 +610,140 @@ class CompiledModel:
                     refuse(name, where)
                 if not np.array_equal(tables(id0, id_step, bins, lim, thr, (name,))[name], ref[name]):
                     refuse(name, " asked for alone" + where)
+        return True
+
+    # ---- the weighted predictive program: weighted_predictive_kernel around the source (predictive.check_weighted) ---------------
+    WEIGHTED_PREDICTIVE = "weighted_predictive"
+
+    def weighted_predictive_program(self):
+        """The handle of the weighted predictive program (glabc_rtc_compile_weighted_predictive; a program of its own in the cache),
+        compiled once and self-checked (self_check_weighted_predictive) before it is handed out; a failed check raises
+        SimulatorSelfCheckError, releases the program and is remembered.  Any prior will do: theta comes from the draws."""
+        key = (self.WEIGHTED_PREDICTIVE,)
+        if key in self._failed:
+            raise SimulatorSelfCheckError(self._failed[key])
+        if key in self._uncompiled:                      # a source that did not compile is not handed to hiprtc again
+            raise SimulatorCompileError(self._uncompiled[key])
+        if key not in self._programs:
+            handle = C.c_void_p()
+            log = C.create_string_buffer(1 << 16)
+            rc = _capi.lib().glabc_rtc_compile_weighted_predictive(self.simulator_source.encode(), self.theta_dim, self.y_dim,
+                                                                   self.noise_dim, C.byref(handle), log, len(log))
+            if rc != _capi.OK:
+                message = "glabc_rtc_compile_weighted_predictive failed (status %d):\n%s" % (rc, log.value.decode(errors="replace"))
+                if rc == _capi.ERR_ARG:                  # the source's own defect; no device (GLABC_ERR_NO_DEVICE) may be there next time
+                    self._uncompiled[key] = message
+                raise SimulatorCompileError(message)
+            self._programs[key] = handle
+        if key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
+            try:
+                self.self_check_weighted_predictive(self._programs[key])
+                self._checked.add(key)
+            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
+                handle = self._programs.pop(key, None)
+                if handle is not None:
+                    _capi.lib().glabc_rtc_release(handle)
+                if isinstance(exc, SimulatorSelfCheckError):
+                    self._failed[key] = str(exc)
+                raise
+        return self._programs[key]
+
+    def self_check_weighted_predictive(self, handle, seed=20240229):
+        """weighted_predictive_kernel of a freshly compiled weighted predictive program against integer sums of the multiplicity m over
+        the draws that glabc_rtc_predictive_draws of this Model's predictive program (itself checked against the composition that
+        specifies a draw) makes for the same ids: 65 + 64 + 1 draws behind a stride that is no multiple of 4, NaN in the padding and
+        behind the last weight; ids that cross 2^32 inside the call and a second run past 2^40; under the scale 0.5, ordinary weights,
+        an exact 0 on a draw whose theta is NaN, a tie (w scale = 2.5, counted twice) and two draws of multiplicity 2^31, which the
+        second table of every run (one bin over the whole range, every threshold +inf) holds in one bin and one tail, where 32-bit
+        counters would wrap.  counts, tails and extremes -- together, then each table alone -- against predictive._torch_tables' bin
+        arithmetic with m for 1 (predictive._torch_weighted_tables) and glabc_key_counts' key, as equal integers.  Runs once per Model
+        (a few ms); GLABC_RTC_SELF_CHECK=0 skips it."""
+        from . import predictive, weighted
+        lib, dev = _capi.lib(), engine.require_device(None)
+        desc = self.descriptor()
+        reference = self.predictive_program()
+        d, yd, k = self.theta_dim, self.y_dim, self.y_dim + 1
+        n, stride, scale = 65 + 64 + 1, 65 + 64 + 1 + 17, 0.5
+        g = torch.Generator().manual_seed(seed)
+        theta = (1.0 + 0.5 * torch.randn(d, n, generator=g, dtype=torch.float64)).to(torch.float32)
+        w = (1.0 + 15.0 * torch.rand(n, generator=g, dtype=torch.float64)).to(torch.float32)
+        w[3], theta[:, 3] = 0.0, float("nan")             # no weight: skipped whatever theta holds
+        w[7] = 5.0                                        # w scale = 2.5: a tie, to even
+        w[20] = w[101] = 2.0 ** 32                        # m = 2^31 each
+        buf = torch.full((d, stride), float("nan"), dtype=torch.float32)
+        buf[:, :n] = theta
+        buf = buf.to(dev)
+        wbuf = torch.full((n + 5,), float("nan"), dtype=torch.float32)
+        wbuf[:n] = w
+        wbuf = wbuf.to(dev)
+        m = weighted._multiplicity(wbuf[:n], scale)
+        if [int(m[3]), int(m[7]), int(m[20]), int(m[101])] != [0, 2, 2 ** 31, 2 ** 31]:
+            raise SimulatorSelfCheckError("the quantised weights of the self-check are not what include/glabc.h specifies")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+        def refuse(name, detail=""):
+            raise SimulatorSelfCheckError(
+                "the run-time compiled weighted_predictive_kernel disagrees with the weighted sums over the draws of the predictive "
+                "program in `%s`%s: refusing to check with it (use path='generic', and please report the simulator source)" % (name, detail))
+
+        def tables(id0, bins, lim, thr, want):
+            counts = torch.zeros(k, bins + 3, dtype=torch.int64, device=dev) if "counts" in want else None
+            tails = torch.zeros(k, 4, dtype=torch.int64, device=dev) if "tails" in want else None
+            extremes = (torch.from_numpy(np.array([predictive.KEY_NONE] * k, np.uint32).view(np.int32)).to(dev)
+                        if "extremes" in want else None)
+            lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+            ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+            with torch.cuda.device(dev):
+                _capi.check(lib.glabc_rtc_weighted_predictive_counts(
+                    handle, C.byref(desc), buf.data_ptr(), stride, d, wbuf.data_ptr(), n, scale, seed, id0, bins,
+                    lo.ctypes.data if counts is not None else None, hi.ctypes.data if counts is not None else None,
+                    thr.ctypes.data if tails is not None else None, ptr(counts), ptr(tails), ptr(extremes), stream),
+                    "glabc_rtc_weighted_predictive_counts")
+            out = {}
+            if counts is not None:
+                out["counts"] = counts.cpu().numpy().view(np.uint64)
+            if tails is not None:
+                out["tails"] = tails.cpu().numpy().view(np.uint64)
+            if extremes is not None:
+                out["extremes"] = extremes.cpu().numpy().view(np.uint32)
+            return out
+
+        for id0 in (2 ** 32 - 40, 2 ** 40 + 5):
+            y = torch.empty(1, yd, n, dtype=torch.float32, device=dev)
+            dis = torch.empty(1, n, dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _capi.check(lib.glabc_rtc_predictive_draws(reference, C.byref(desc), buf.data_ptr(), 1, d, n, stride, seed, id0, n,
+                                                           y.data_ptr(), n, dis.data_ptr(), n, stream), "glabc_rtc_predictive_draws")
+            stats = torch.cat([y[0].t(), dis[0].reshape(-1, 1)], dim=1)
+            host, mult = stats.cpu().numpy(), m.cpu().numpy()
+            lim, thr, whole = np.empty((k, 2)), np.empty(k, np.float32), np.empty((k, 2))
+            extremes = np.array([predictive.KEY_NONE] * k, np.uint32)
+            for j in range(k):
+                counted = host[:, j][mult > 0]
+                v = np.sort(counted[np.isfinite(counted)])
+                if v.size == 0:
+                    lim[j], thr[j], whole[j] = (0.0, 1.0), 0.0, (0.0, 1.0)
+                else:
+                    lim[j], thr[j] = (float(v[v.size // 10]), float(v[9 * v.size // 10])), v[v.size // 2]
+                    whole[j] = float(v[0]), float(v[-1])
+                for pair in (lim[j], whole[j]):
+                    if not pair[0] < pair[1]:
+                        pair[:] = pair[0] - 0.5, pair[0] + 0.5
+                v = counted[~np.isnan(counted)]
+                if v.size:                                             # include/glabc.h glabc_key_counts: -0 is +0, order-preserving
+                    u = np.where(v == 0, np.float32(0.0), v).astype(np.float32).view(np.uint32)
+                    keys = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+                    extremes[j] = keys.min(), keys.max()
+            for bins, edges, levels in ((7, lim, thr), (1, whole, np.full(k, np.inf, np.float32))):
+                where = " (id0 %d, %d bins)" % (id0, bins)
+                ref = dict(zip(("counts", "tails"), predictive._torch_weighted_tables(stats, m, bins, edges, levels)))
+                ref["extremes"] = extremes
+                got = tables(id0, bins, edges, levels, ("counts", "tails", "extremes"))
+                for name in ("counts", "tails", "extremes"):
+                    if not np.array_equal(got[name], ref[name]):
+                        refuse(name, where)
+                    if not np.array_equal(tables(id0, bins, edges, levels, (name,))[name], ref[name]):
+                        refuse(name, " asked for alone" + where)
         return True
 
     def _gamma_prior(self):

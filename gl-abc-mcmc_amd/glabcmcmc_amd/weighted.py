@@ -34,7 +34,9 @@ uses the same ``scale``: a sharded job all-reduces ``key_counts`` inside the ``c
 counts of ``histogram`` / ``histogram2d``.  ``terms`` reduces a shard to the additive statistics of ``summary``'s mean, sd and
 effective sample size, ``combine`` adds shards, ``moments`` evaluates them.
 
-Out of scope: weights on (T, C, D) chain histories, weighted predictive checks, weighted R-hat / ESS of chains, an interpolating
+Posterior predictive checks of weighted draws are ``predictive.check_weighted``, on the same quantised weights.
+
+Out of scope: weights on (T, C, D) chain histories, weighted R-hat / ESS of chains, an interpolating
 weighted quantile, a kernel for the weighted mean and covariance (``regression.terms`` holds sum w, sum w theta and
 sum w theta theta^T in specified bits), float64 weights in the kernels (they are cast to float32, as everywhere in the package).
 """

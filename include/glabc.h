@@ -1203,6 +1203,60 @@ int glabc_weighted_histogram(const float* x, int64_t stride, int32_t dim, const 
 int glabc_weighted_histogram2d(const float* x, int64_t stride, int32_t dim, const float* w, int64_t n, double scale, int32_t n_pairs,
                                const int32_t* pairs, int32_t n_bins, const double* lo, const double* hi, uint64_t* counts, void* stream);
 
+/* ---- posterior predictive checks of weighted draws (csrc/glabc_weighted_predictive.hip, glabcmcmc_amd/predictive.py check_weighted):
+ * glabc_predictive_counts for n draws with one float32 weight each -- an ABC-SMC population, regression-adjusted draws -- one fused
+ * kernel.  x is dimension-major as the weighted entry points above read it, x[j * stride + i], j < theta_dim, i < n, stride >= n;
+ * columns n .. stride - 1 are never read, nor is anything behind w[n - 1]; both bases need 4-byte alignment only.  w[i] is a device
+ * array of n float32 weights, `scale` a positive finite double of the host's.
+ *
+ * Specification.  Draw i has the id id0 + i and is exactly the draw (row 0, chain i) that glabc_predictive_draws makes on the history
+ * [1][theta_dim][stride] with n_chains = n and the same model, seed and id0: the same key (seed ^ GLABC_PREDICTIVE_KEY), the same
+ * noise, the same simulator, the same distance -- the same bits as the unweighted twin's draw, whatever the launch geometry and
+ * however the draws were cut into calls (a slice that starts at draw a passes id0 + a).  Draw i counts with the quantised weight
+ * m_i = weight_multiplicity(w_i, scale) of the weighted entry points above.  A draw with m_i == 0 is skipped whatever theta holds: it
+ * adds nothing to any count, to any tail (the NaN tail included) or to the extremes.
+ *
+ * The three tables are laid out as glabc_predictive_counts lays them out, with K = y_dim + 1 statistics (y, then the distance):
+ *     counts[k * (n_bins + 3) + slot]   uint64.  The same slot rule; a draw adds m_i where the twin adds 1
+ *     tails[k * 4 + s]                  uint64.  The same four classes against threshold[k]; a draw adds m_i where the twin adds 1
+ *     extremes[k * 2 + {0, 1}]          uint32.  atomicMin / atomicMax of the key over the draws with m_i > 0 whose statistic is no NaN
+ * The call ADDS: the caller zeroes counts and tails and pre-sets the extremes to 0xFFFFFFFF / 0.  Each of the three may be NULL, not
+ * all of them.  lo, hi and threshold are HOST arrays as in the twin.  With every weight 1.0 and scale 1.0 the three tables equal
+ * glabc_predictive_counts' on that one-row history.  n <= GLABC_MAX_WEIGHTED_DRAWS draws of at most 2^32 - 1 each stay below 2^63:
+ * no uint64 wraps, by the argument of the weighted summaries above.
+ *
+ * GLABC_MAX_WEIGHTED_PREDICTIVE_BINS is 512 where the twin has 1024.  The counters in LDS are 64-bit (two draws of multiplicity 2^31
+ * wrap a uint32), and the tails take four more per statistic: 1024 bins at K = 9 would need 9 x 1031 x 8 = 74 232 bytes, past the 48 KiB
+ * a launch gets without a grant (csrc/glabc_lds_grant.h).  512 bins keep the largest table at 9 x (512 + 3 + 4) x 8 = 37 368 bytes,
+ * which holds for the built-in launch and for the hipModuleLaunchKernel of a run-time compiled program alike; nothing here shows that
+ * a grant takes effect on a module function, so the limit is one that needs none.
+ *
+ * Refusals, in the twins' order; a refused call launches nothing and writes nothing:
+ *   a NULL model, x or w, all outputs NULL, counts without lo or hi, tails without threshold      GLABC_ERR_NULL
+ *   the Model and dimension refusals of glabc_predictive_counts                                   GLABC_ERR_DIM, GLABC_ERR_KIND
+ *   n < 0, n > GLABC_MAX_WEIGHTED_DRAWS, stride < n, a scale that is not finite or not > 0; id0 < 0 or id0 + n - 1 past int64; with
+ *   counts: n_bins outside 1 .. GLABC_MAX_WEIGHTED_PREDICTIVE_BINS, a lo or hi that is not finite or not lo < hi; with tails: a NaN
+ *   threshold                                                                                     GLABC_ERR_ARG
+ * n == 0 returns GLABC_OK and writes nothing.  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no struct changes.
+ *
+ * The run-time compiled twin.  glabc_rtc_compile_weighted_predictive compiles the same kernel template around a USER simulator: a
+ * program kind of its own (it holds the weighted kernel and the two row kernels every program holds, and no other entry point
+ * launches it), compiled, logged and released as glabc_rtc_compile_predictive's.  glabc_rtc_weighted_predictive_counts is
+ * glabc_weighted_predictive_counts on such a program: draw i is the draw of glabc_rtc_predictive_draws of the predictive program of
+ * the same source, the distance the user's where the source announces GLABC_USER_DISCREPANCY.  Its refusals are a NULL program
+ * (GLABC_ERR_NULL), glabc_rtc_predictive_counts' of a program of another kind or shape, then the list above. */
+#define GLABC_MAX_WEIGHTED_PREDICTIVE_BINS 512
+int glabc_weighted_predictive_counts(const glabc_model* model, const float* x, int64_t stride, int32_t theta_dim, const float* w,
+                                     int64_t n, double scale, uint64_t seed, int64_t id0, int32_t n_bins, const double* lo,
+                                     const double* hi, const float* threshold, uint64_t* counts, uint64_t* tails, uint32_t* extremes,
+                                     void* stream);
+int glabc_rtc_compile_weighted_predictive(const char* simulator_source, int32_t theta_dim, int32_t y_dim, int32_t noise_dim,
+                                          glabc_rtc_program** out, char* log, int64_t log_size);
+int glabc_rtc_weighted_predictive_counts(const glabc_rtc_program* program, const glabc_model* model, const float* x, int64_t stride,
+                                         int32_t theta_dim, const float* w, int64_t n, double scale, uint64_t seed, int64_t id0,
+                                         int32_t n_bins, const double* lo, const double* hi, const float* threshold, uint64_t* counts,
+                                         uint64_t* tails, uint32_t* extremes, void* stream);
+
 /* AGLMCMC.py:199-204 (and :104-109): weights of a proposal pool from its stored discrepancies,
  * w[r] = exp((prior(theta_r) + calculate_log_kernel_dis(dis_r)) - log_q[r]), NaN -> 0.  The threshold is the one in
  * model->kern_* (the caller passes a copy of its descriptor with the annealed eps_hat, Mixture.py:47-53).
