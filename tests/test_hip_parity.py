@@ -1366,23 +1366,101 @@ def test_config_1_runner_global_mcmc_one_chain_10000_iterations(hip, oracle, tmp
 
 
 # ---------------------------------------------------------------------------------- GLABC_MATH_FAST (opt-in), teacher-forced parity
-def _fast_run(model, local, glob, theta0, y0, T, seed, gf, N, chain0=0, dump=True, moments=False):
+TAPE_GUARD = 256                # canary elements in front of and behind every tape buffer
+
+
+def _fast_run(model, local, glob, theta0, y0, T, seed, gf, N, chain0=0, dump=True, moments=False, step0=1, chains=None):
+    """One GLABC_MATH_FAST launch of T iterations from iteration step0 -> (history, chains, moments, tape).  chains: the
+    ChainBatch an earlier launch left (None: a fresh one from theta0 / y0 after init_weights); moments: True, or the
+    engine.Moments an earlier launch filled.  The tape buffers start as NaN and lie inside larger canary buffers: the guards
+    must come back untouched (checked here), and whatever the kernel does not write stays NaN for the caller to find."""
     from glabcmcmc_amd import _capi as A
     from glabcmcmc_amd import engine
+    import helpers as H
     dev = torch.device("cuda", 0)
-    chains = engine.ChainBatch(torch.from_numpy(theta0), torch.from_numpy(y0), dev, chain0=chain0)
-    engine.init_weights(model, glob, chains)
+    if chains is None:
+        chains = engine.ChainBatch(torch.from_numpy(theta0), torch.from_numpy(y0), dev, chain0=chain0)
+        engine.init_weights(model, glob, chains)
     n, d, yd = chains.n, chains.d, chains.yd
     hist = torch.empty(T, d, n, dtype=torch.float32, device=dev)
-    tape = None
+    tape, whole = None, []
     if dump:
-        tape = (torch.zeros(n, T, 2, dtype=torch.float32, device=dev), torch.zeros(n, T, dtype=torch.float64, device=dev),
-                torch.zeros(n, T, N, d + yd, dtype=torch.float32, device=dev))
-    mom = engine.Moments(n, d, dev) if moments else None
-    engine.run_steps("glabc_glmcmc_steps", model, local, glob, chains, T, 1, seed, gf, N, history=hist, moments=mom,
+        def guarded(canary, *shape):
+            size = int(np.prod(shape))
+            flat = H.dev(canary(size + 2 * TAPE_GUARD))
+            body = flat[TAPE_GUARD:TAPE_GUARD + size].view(*shape)
+            body.fill_(float("nan"))
+            whole.append((flat, size))
+            return body
+        tape = (guarded(H.canary_f32, n, T, 2), guarded(H.canary_f64, n, T), guarded(H.canary_f32, n, T, N, d + yd))
+    mom = engine.Moments(n, d, dev) if moments is True else (moments or None)
+    engine.run_steps("glabc_glmcmc_steps", model, local, glob, chains, T, step0, seed, gf, N, history=hist, moments=mom,
                      math_mode=A.MATH_FAST, dump_draws=tape)
     torch.cuda.synchronize()
+    for flat, size in whole:
+        edge = flat.cpu().numpy()
+        H.assert_untouched(edge[:TAPE_GUARD], edge[TAPE_GUARD + size:])
     return hist.cpu().numpy(), chains, mom, None if tape is None else tuple(t.cpu().numpy() for t in tape)
+
+
+def fast_replay(oracle, model, local, glob, theta0, y0, gf, N, tapes, idx=None, chain0=0, seed=0, moments=False):
+    """The CPU checker, in exact arithmetic, on the draws a fast kernel recorded.  tapes: one (u, r, z) per launch, in order;
+    launch k starts at iteration 1 + (the lengths before it) from the state the replay of launch k - 1 left, the first from
+    (theta0, y0) after oracle_init_weights.  idx: the chains to replay (None: all).  -> (history (T, d, len(idx)), HostChains,
+    HostMoments or None)"""
+    idx = np.arange(theta0.shape[0]) if idx is None else np.asarray(idx)
+    d = theta0.shape[1]
+    hc = oracle_lib.HostChains(theta0[idx], y0[idx], chain0=chain0)
+    mom = oracle_lib.HostMoments(len(idx), d) if moments else None
+    cs = hc.struct()
+    assert oracle.oracle_init_weights(C.byref(model), C.byref(glob), C.byref(cs)) == 0
+    rows, step0 = [], 1
+    for u, r, z in tapes:
+        T = u.shape[1]
+        hh = np.zeros((T, d, len(idx)), np.float32)
+        run, keep = oracle_lib.make_run(seed=seed, step0=step0, n_steps=T, gf=gf, batch=N, history=hh, moments=mom,
+                                        tape=(np.ascontiguousarray(u[idx]), np.ascontiguousarray(r[idx]),
+                                              np.ascontiguousarray(z[idx]), N))
+        assert oracle.oracle_glmcmc_steps(C.byref(model), C.byref(local), C.byref(glob), C.byref(cs), C.byref(run)) == 0
+        rows.append(hh)
+        step0 += T
+    return np.concatenate(rows, axis=0), hc, mom
+
+
+def fast_flips(oracle, model, local, glob, theta0, y0, gf, N, tapes, hist, hh, **kw):
+    """Chains whose kernel history `hist` leaves the checker's replay `hh` of the kernel's own draws (fast_replay of `tapes`), and
+    which of them the perturbation replay does NOT explain: a chain is explained when replaying it with the resampling uniform
+    of its first differing iteration moved by +-1e-5, or that iteration's accept uniform scaled by exp(+-2e-3), gives the
+    kernel's state of that iteration.  -> (flipped chain indices, [(chain, first differing iteration)] unexplained)"""
+    flipped = np.flatnonzero((bits(hist) != bits(hh)).any(axis=(0, 1)))
+    starts = np.cumsum([0] + [t[0].shape[1] for t in tapes])
+    unexplained = []
+    for c in flipped:
+        t0 = int(np.flatnonzero((bits(hist[:, :, c]) != bits(hh[:, :, c])).any(axis=1))[0])
+        k = int(np.searchsorted(starts, t0, side="right")) - 1              # the launch of iteration t0 and its row there
+        tl = t0 - int(starts[k])
+        ok = False
+        for dr, fu in ((1e-5, 1.0), (-1e-5, 1.0), (0.0, float(np.exp(2e-3))), (0.0, float(np.exp(-2e-3)))):
+            mine = [tuple(a[c:c + 1].copy() for a in t) for t in tapes]
+            u2, r2, _ = mine[k]
+            r2[0, tl] = min(max(r2[0, tl] + dr, 0.0), 1.0 - 2 ** -53)
+            u2[0, tl, 1] = np.float32(min(u2[0, tl, 1] * fu, 1.0 - 2 ** -24))
+            h2, _, _ = fast_replay(oracle, model, local, glob, theta0[c:c + 1], y0[c:c + 1], gf, N, mine, **kw)
+            ok = ok or np.array_equal(bits(h2[t0, :, 0]), bits(hist[t0, :, c]))
+        if not ok:
+            unexplained.append((int(c), t0))
+    return flipped, unexplained
+
+
+def assert_same_fast_state(chains, hc, keep):
+    """theta, y, n_moves and flags of the chains `keep` equal the replay's bit for bit (assert_same_state on that subset; log_w is
+    a function of the fast kernel's own K(y) and is compared within a bound by the callers that look at it)"""
+    from types import SimpleNamespace
+    k = torch.from_numpy(np.asarray(keep))
+    got = SimpleNamespace(theta=chains.theta.cpu()[:, k], y=chains.y.cpu()[:, k], n_moves=chains.n_moves.cpu()[k])
+    want = SimpleNamespace(theta=hc.theta[:, keep], y=hc.y[:, keep], n_moves=hc.n_moves[keep])
+    assert_same_state(got, want, False)
+    assert np.array_equal(chains.flags.cpu().numpy().astype(np.uint32)[keep], hc.flags[keep])
 
 
 FAST_CASES = [
@@ -1423,38 +1501,18 @@ def test_fast_math_decisions_follow_the_checker_on_the_kernels_own_draws(hip, or
     theta0 = rng.standard_normal((n, d)).astype(np.float32)
     y0 = (np.abs(theta0) + 0.2236068 * rng.standard_normal((n, d))).astype(np.float32)
     hist, chains, _, (tu, tr, tz) = _fast_run(model, local, glob, theta0, y0, T, seed, gf, N, chain0=77)
+    assert np.isfinite(tu).all() and np.isfinite(tr).all()                       # the tape starts as NaN: every slot was written
     assert np.isfinite(tz).all() and abs(tz.mean()) < 0.05 if gspec[0] == "gauss" else True
+    assert np.isfinite(tz).all()
 
-    def replay(idx, u, r, z):
-        """the checker on the tape rows of chains idx -> history (T, d, len(idx))"""
-        hc = oracle_lib.HostChains(theta0[idx], y0[idx], chain0=77)
-        hh = np.zeros((T, d, len(idx)), np.float32)
-        run, keep = oracle_lib.make_run(seed=seed, step0=1, n_steps=T, gf=gf, batch=N, history=hh,
-                                        tape=(np.ascontiguousarray(u), np.ascontiguousarray(r), np.ascontiguousarray(z), N))
-        cs = hc.struct()
-        assert oracle.oracle_init_weights(C.byref(model), C.byref(glob), C.byref(cs)) == 0
-        assert oracle.oracle_glmcmc_steps(C.byref(model), C.byref(local), C.byref(glob), C.byref(cs), C.byref(run)) == 0
-        return hh
-
-    hh = replay(np.arange(n), tu, tr, tz)
-    differ = (bits(hist) != bits(hh)).any(axis=(0, 1))
+    hh, hc, _ = fast_replay(oracle, model, local, glob, theta0, y0, gf, N, [(tu, tr, tz)], chain0=77, seed=seed)
     moved = (np.diff(hist, axis=0) != 0).any(axis=1).sum()
     assert moved > n                                                             # the run does something
-    flipped = np.flatnonzero(differ)
+    flipped, unexplained = fast_flips(oracle, model, local, glob, theta0, y0, gf, N, [(tu, tr, tz)], hist, hh,
+                                      chain0=77, seed=seed)
     assert len(flipped) <= max(4, n // 200), "%d of %d chains leave the checker's path" % (len(flipped), n)
-    unexplained = []
-    for c in flipped:
-        t0 = int(np.flatnonzero((bits(hist[:, :, c]) != bits(hh[:, :, c])).any(axis=1))[0])
-        ok = False
-        for dr, fu in ((1e-5, 1.0), (-1e-5, 1.0), (0.0, float(np.exp(2e-3))), (0.0, float(np.exp(-2e-3)))):
-            u2, r2 = tu[c:c + 1].copy(), tr[c:c + 1].copy()
-            r2[0, t0] = min(max(r2[0, t0] + dr, 0.0), 1.0 - 2 ** -53)
-            u2[0, t0, 1] = np.float32(min(u2[0, t0, 1] * fu, 1.0 - 2 ** -24))
-            h2 = replay(np.array([c]), u2, r2, tz[c:c + 1])
-            ok = ok or np.array_equal(bits(h2[t0, :, 0]), bits(hist[t0, :, c]))
-        if not ok:
-            unexplained.append((int(c), t0))
     assert not unexplained, "decisions that differ beyond rounding of their threshold: %s" % unexplained[:5]
+    assert_same_fast_state(chains, hc, np.setdiff1d(np.arange(n), flipped))      # what the kernel leaves behind, where it followed
     print("fast math d=%d N=%d: %d of %d chains take a within-rounding decision the other way in %d iterations"
           % (d, N, len(flipped), n, T))
 
