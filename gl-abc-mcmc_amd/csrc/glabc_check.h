@@ -574,7 +574,7 @@ inline int check_rtc_run(const RtcShape& p, const glabc_model* m, const glabc_di
 }
 
 // ---- glabc_rtc_mix_steps: a launch of the run-time compiled MIXTURE program of shape `p` ----------------------------------------
-// mix_program: the program was built from the mixture table (glabc_rtc_compile_mix / _wide_mix, glabc_rtc_mix_kernels.h); a program of
+// mix_program: the program was built from the mixture table (glabc_rtc_compile_mix / _wide_mix, rtc_mix_kernels of glabc_rtc_tables.h); a program of
 // the other table holds no kernel that takes a MixStepArgs.  The order is the contract (include/glabc.h).
 inline int check_rtc_mix_run(const RtcShape& p, bool mix_program, const glabc_model* m, const glabc_dist* local, const glabc_mixture* g,
                              const glabc_chains* c, const glabc_run* r)
@@ -604,7 +604,7 @@ inline int check_rtc_mix_run(const RtcShape& p, bool mix_program, const glabc_mo
 }
 
 // ---- glabc_rtc_abc_draws / glabc_rtc_smc_draws: a launch of the run-time compiled DRAWS program of shape `p` -------------------------
-// draws_program: the program was built from the draws table (glabc_rtc_compile_draws, glabc_rtc_draws_kernels.h); no other program
+// draws_program: the program was built from the draws table (glabc_rtc_compile_draws, rtc_draws_kernels of glabc_rtc_tables.h); no other program
 // holds a draw kernel.  any_output: one of the entry point's outputs is not NULL.  smc: glabc_rtc_smc_draws, which reads `pop` --
 // refused as glabc_smc_draws refuses it (check_draw_population), between the Model and the range of draws; the prior is
 // check_draw_prior's, the range check_abc_range's.  The order is the contract (include/glabc.h); the entry point has refused a NULL program before.
@@ -624,7 +624,7 @@ inline int check_rtc_draws(const RtcShape& p, bool draws_program, const glabc_mo
 }
 
 // ---- glabc_rtc_predictive_draws / glabc_rtc_predictive_counts: a launch of the run-time compiled PREDICTIVE program of shape `p` -------
-// pred_program: the program was built from the predictive table (glabc_rtc_compile_predictive, glabc_rtc_predictive_kernels.h); no
+// pred_program: the program was built from the predictive table (glabc_rtc_compile_predictive, rtc_predictive_kernels of glabc_rtc_tables.h); no
 // other program holds predictive_kernel.  The entry point has refused a NULL program before; after this, check_predictive_draws /
 // check_predictive_counts with PredModelCheck{true} refuse what the built-in entry points refuse, in their order.  The prior is not
 // looked at: theta comes from the history.  The order is the contract (include/glabc.h).

@@ -32,4 +32,11 @@ int dispatch_range(int v, int not_found, F&& f)
     return dispatch_offsets<Lo>(v, not_found, f, std::make_integer_sequence<int, Hi - Lo + 1>{});
 }
 
+// two run-time integers of the same range at once: f(integral_constant<int, A>, integral_constant<int, B>)
+template <int Lo, int Hi, class F>
+int dispatch_pair(int a, int b, int not_found, F&& f)
+{
+    return dispatch_range<Lo, Hi>(a, not_found, [&](auto A) { return dispatch_range<Lo, Hi>(b, not_found, [&](auto B) { return f(A, B); }); });
+}
+
 }  // namespace glabc

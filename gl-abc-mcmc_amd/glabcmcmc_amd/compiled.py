@@ -130,38 +130,54 @@ class CompiledModel:
         check = (algo, n)                                # its self-check: once per batch size (the wide one serves many)
         if gamma:
             key, check = key + (self.GAMMA,), check + (self.GAMMA,)
+        flags = _capi.RTC_GAMMA if gamma else 0
+        if wide:
+            compile_call = ("glabc_rtc_compile_wide_ex", lambda src: (src, self.theta_dim, self.y_dim, self.noise_dim, flags))
+        else:
+            compile_call = ("glabc_rtc_compile_ex", lambda src: (src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, flags))
+        # the wide program is one code object for all batch sizes above 16: the checks it passed at other batch sizes go with it
+        siblings = (lambda k: k[0] == algo and k[1] > _capi.MAX_BATCH and len(k) == len(check)) if wide else None
+        run_check = (lambda handle: self.self_check(algo, n, gamma=True, proposal=proposal)) if gamma else (lambda handle: self.self_check(algo, n))
+        return self._cached_program(key, compile_call, run_check, check_key=check, check_reenters=True, siblings=siblings)
+
+    def _cached_program(self, key, compile_call, check, check_key=None, check_reenters=False, remember_uncompiled=False, siblings=None):
+        """The cache protocol of every program kind -> the handle under `key`, compiled once and self-checked before it is handed out.
+        compile_call: (entry point, source -> its arguments before `out, log, log_size`), looked at only when there is something to
+        compile; a status other than OK raises SimulatorCompileError with the compiler's log.  check(handle): the self-check, once per `check_key` (default: the key; the wide programs serve many batch
+        sizes and are checked once for each), skipped under GLABC_RTC_SELF_CHECK=0.  A program that failed (or did not finish) its
+        check must never be handed out: it is released, and a SimulatorSelfCheckError is remembered, so that every later call raises
+        again instead of running a miscompiled kernel.
+        check_reenters: the check comes back into program() for this very key (through the samplers), so the check key is marked
+        before it runs and taken back if it fails; otherwise it is marked once the check has passed.
+        remember_uncompiled: an ERR_ARG compile -- the source's own defect -- is remembered too, and the source not handed to hiprtc
+        again (no device, GLABC_ERR_NO_DEVICE, may be there next time).
+        siblings: of a failing wide program, which other passed checks go with it (a predicate on check keys)."""
+        check_key = key if check_key is None else check_key
         if key in self._failed:
             raise SimulatorSelfCheckError(self._failed[key])
+        if key in self._uncompiled:
+            raise SimulatorCompileError(self._uncompiled[key])
         if key not in self._programs:
+            name, arguments = compile_call
             handle = C.c_void_p()
             log = C.create_string_buffer(1 << 16)
-            src = self.simulator_source.encode()
-            flags = _capi.RTC_GAMMA if gamma else 0
-            if wide:
-                name = "glabc_rtc_compile_wide_ex"
-                rc = _capi.lib().glabc_rtc_compile_wide_ex(src, self.theta_dim, self.y_dim, self.noise_dim, flags, C.byref(handle), log,
-                                                           len(log))
-            else:
-                name = "glabc_rtc_compile_ex"
-                rc = _capi.lib().glabc_rtc_compile_ex(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, flags, C.byref(handle),
-                                                      log, len(log))
+            rc = getattr(_capi.lib(), name)(*arguments(self.simulator_source.encode()), C.byref(handle), log, len(log))
             if rc != _capi.OK:
-                raise SimulatorCompileError("%s failed (status %d):\n%s" % (name, rc, log.value.decode(errors="replace")))
+                message = "%s failed (status %d):\n%s" % (name, rc, log.value.decode(errors="replace"))
+                if remember_uncompiled and rc == _capi.ERR_ARG:
+                    self._uncompiled[key] = message
+                raise SimulatorCompileError(message)
             self._programs[key] = handle
-        if check not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
-            self._checked.add(check)                     # before the check: self_check re-enters program() through the samplers
+        if check_key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
+            if check_reenters:
+                self._checked.add(check_key)
             try:
-                if gamma:
-                    self.self_check(algo, n, gamma=True, proposal=proposal)
-                else:
-                    self.self_check(algo, n)
+                check(self._programs[key])
+                self._checked.add(check_key)
             except BaseException as exc:
-                # a program that failed (or did not finish) its check must never be handed out: release it, and keep the
-                # verdict so that every later call raises again instead of sampling with a miscompiled kernel.  The wide program
-                # is one code object for all batch sizes above 16: the checks it passed at other batch sizes go with it
-                self._checked.discard(check)
-                if wide:
-                    self._checked -= {k for k in self._checked if k[0] == algo and k[1] > _capi.MAX_BATCH and len(k) == len(check)}
+                self._checked.discard(check_key)
+                if siblings is not None:
+                    self._checked -= {k for k in self._checked if siblings(k)}
                 handle = self._programs.pop(key, None)
                 if handle is not None:
                     _capi.lib().glabc_rtc_release(handle)
@@ -169,6 +185,10 @@ class CompiledModel:
                     self._failed[key] = str(exc)
                 raise
         return self._programs[key]
+
+    def _source_and_dimensions(self, src):
+        """the arguments of the compile entry points that take no more than these"""
+        return src, self.theta_dim, self.y_dim, self.noise_dim
 
     def _mixture_program(self, algo, batch_size, proposal=None):
         n = 1 if algo == _capi.ALGO_GLOBALMCMC else int(batch_size)
@@ -178,38 +198,14 @@ class CompiledModel:
         if self._gamma_prior():
             raise ValueError("the mixture variant knows no Gamma prior")
         key = (algo, self.WIDE if wide else n, self.MIXTURE)
-        if key in self._failed:
-            raise SimulatorSelfCheckError(self._failed[key])
-        if key not in self._programs:
-            handle = C.c_void_p()
-            log = C.create_string_buffer(1 << 16)
-            src = self.simulator_source.encode()
-            if wide:
-                name = "glabc_rtc_compile_wide_mix"
-                rc = _capi.lib().glabc_rtc_compile_wide_mix(src, self.theta_dim, self.y_dim, self.noise_dim, C.byref(handle), log, len(log))
-            else:
-                name = "glabc_rtc_compile_mix"
-                rc = _capi.lib().glabc_rtc_compile_mix(src, algo, self.theta_dim, self.y_dim, self.noise_dim, n, C.byref(handle), log,
-                                                       len(log))
-            if rc != _capi.OK:
-                raise SimulatorCompileError("%s failed (status %d):\n%s" % (name, rc, log.value.decode(errors="replace")))
-            self._programs[key] = handle
         check = (algo, n, self.MIXTURE)                  # the self-check: once per batch size, as for the other programs
-        if check not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
-            self._checked.add(check)                     # before the check: it re-enters program() through the samplers
-            try:
-                self.self_check_mixture(algo, n, proposal)
-            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
-                self._checked.discard(check)
-                if wide:
-                    self._checked -= {k for k in self._checked if k[0] == algo and k[-1] == self.MIXTURE and k[1] > _capi.MAX_BATCH}
-                handle = self._programs.pop(key, None)
-                if handle is not None:
-                    _capi.lib().glabc_rtc_release(handle)
-                if isinstance(exc, SimulatorSelfCheckError):
-                    self._failed[key] = str(exc)
-                raise
-        return self._programs[key]
+        if wide:
+            compile_call = ("glabc_rtc_compile_wide_mix", self._source_and_dimensions)
+        else:
+            compile_call = ("glabc_rtc_compile_mix", lambda src: (src, algo, self.theta_dim, self.y_dim, self.noise_dim, n))
+        siblings = (lambda k: k[0] == algo and k[-1] == self.MIXTURE and k[1] > _capi.MAX_BATCH) if wide else None
+        return self._cached_program(key, compile_call, lambda handle: self.self_check_mixture(algo, n, proposal), check_key=check,
+                                    check_reenters=True, siblings=siblings)
 
     def self_check_mixture(self, algo, batch_size=1, proposal=None, n_chains=512, steps=4, seed=20240229):
         """self_check for a mixture program: glabc_rtc_mix_steps against the split-phase iteration glabc_propose_mix -> this Model's
@@ -272,28 +268,7 @@ class CompiledModel:
         if reason is not None:
             raise ValueError("no draws program for this Model: " + reason)
         key = (self.DRAWS,)
-        if key in self._failed:
-            raise SimulatorSelfCheckError(self._failed[key])
-        if key not in self._programs:
-            handle = C.c_void_p()
-            log = C.create_string_buffer(1 << 16)
-            rc = _capi.lib().glabc_rtc_compile_draws(self.simulator_source.encode(), self.theta_dim, self.y_dim, self.noise_dim,
-                                                     C.byref(handle), log, len(log))
-            if rc != _capi.OK:
-                raise SimulatorCompileError("glabc_rtc_compile_draws failed (status %d):\n%s" % (rc, log.value.decode(errors="replace")))
-            self._programs[key] = handle
-        if key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
-            try:
-                self.self_check_draws(self._programs[key])
-                self._checked.add(key)
-            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
-                handle = self._programs.pop(key, None)
-                if handle is not None:
-                    _capi.lib().glabc_rtc_release(handle)
-                if isinstance(exc, SimulatorSelfCheckError):
-                    self._failed[key] = str(exc)
-                raise
-        return self._programs[key]
+        return self._cached_program(key, ("glabc_rtc_compile_draws", self._source_and_dimensions), self.self_check_draws)
 
     def composed_draws(self, handle, desc, seed, row0, n, population=None, chol=None):
         """Draws row0 .. row0 + n - 1 as include/glabc.h specifies them, from the entry points a draw is composed of: theta from
@@ -436,7 +411,7 @@ class CompiledModel:
 
     @staticmethod
     def predictive_rows():
-        """rows per item of a predictive program compiled now: csrc/glabc_rtc_predictive_kernels.h rtc_predictive_rows restated
+        """rows per item of a predictive program compiled now: csrc/glabc_rtc_tables.h rtc_predictive_rows restated
         (RTC_PRED_ROWS = 1; GLABC_RTC_PRED_ROWS=1..16 in the environment forces another, any other value is ignored)"""
         try:
             rows = int(os.environ.get("GLABC_RTC_PRED_ROWS", "1"))
@@ -449,35 +424,10 @@ class CompiledModel:
         (self_check_predictive) before it is handed out; a failed check raises SimulatorSelfCheckError, releases the program and is
         remembered.  Any prior will do: theta comes from the history."""
         key = (self.PREDICTIVE,)
-        if key in self._failed:
-            raise SimulatorSelfCheckError(self._failed[key])
-        if key in self._uncompiled:                      # a source that did not compile is not handed to hiprtc again
-            raise SimulatorCompileError(self._uncompiled[key])
         if key not in self._programs:
-            handle = C.c_void_p()
-            log = C.create_string_buffer(1 << 16)
-            rows = self.predictive_rows()
-            rc = _capi.lib().glabc_rtc_compile_predictive(self.simulator_source.encode(), self.theta_dim, self.y_dim, self.noise_dim,
-                                                          C.byref(handle), log, len(log))
-            if rc != _capi.OK:
-                message = "glabc_rtc_compile_predictive failed (status %d):\n%s" % (rc, log.value.decode(errors="replace"))
-                if rc == _capi.ERR_ARG:                  # the source's own defect; no device (GLABC_ERR_NO_DEVICE) may be there next time
-                    self._uncompiled[key] = message
-                raise SimulatorCompileError(message)
-            self._programs[key] = handle
-            self._predictive_rows = rows
-        if key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
-            try:
-                self.self_check_predictive(self._programs[key], rows=self._predictive_rows)
-                self._checked.add(key)
-            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
-                handle = self._programs.pop(key, None)
-                if handle is not None:
-                    _capi.lib().glabc_rtc_release(handle)
-                if isinstance(exc, SimulatorSelfCheckError):
-                    self._failed[key] = str(exc)
-                raise
-        return self._programs[key]
+            self._predictive_rows = self.predictive_rows()               # what a compile now takes
+        return self._cached_program(key, ("glabc_rtc_compile_predictive", self._source_and_dimensions), lambda handle: self.self_check_predictive(handle, rows=self._predictive_rows),
+                                    remember_uncompiled=True)
 
     def composed_predictive(self, handle, desc, hist, seed, id0, id_step):
         """The predictive draws of the chain-major device history `hist` (T, D, C) as include/glabc.h specifies them, from the entry
@@ -620,33 +570,8 @@ class CompiledModel:
         compiled once and self-checked (self_check_weighted_predictive) before it is handed out; a failed check raises
         SimulatorSelfCheckError, releases the program and is remembered.  Any prior will do: theta comes from the draws."""
         key = (self.WEIGHTED_PREDICTIVE,)
-        if key in self._failed:
-            raise SimulatorSelfCheckError(self._failed[key])
-        if key in self._uncompiled:                      # a source that did not compile is not handed to hiprtc again
-            raise SimulatorCompileError(self._uncompiled[key])
-        if key not in self._programs:
-            handle = C.c_void_p()
-            log = C.create_string_buffer(1 << 16)
-            rc = _capi.lib().glabc_rtc_compile_weighted_predictive(self.simulator_source.encode(), self.theta_dim, self.y_dim,
-                                                                   self.noise_dim, C.byref(handle), log, len(log))
-            if rc != _capi.OK:
-                message = "glabc_rtc_compile_weighted_predictive failed (status %d):\n%s" % (rc, log.value.decode(errors="replace"))
-                if rc == _capi.ERR_ARG:                  # the source's own defect; no device (GLABC_ERR_NO_DEVICE) may be there next time
-                    self._uncompiled[key] = message
-                raise SimulatorCompileError(message)
-            self._programs[key] = handle
-        if key not in self._checked and os.environ.get("GLABC_RTC_SELF_CHECK", "1") != "0":
-            try:
-                self.self_check_weighted_predictive(self._programs[key])
-                self._checked.add(key)
-            except BaseException as exc:                 # never hand out a program that failed its check; the verdict sticks
-                handle = self._programs.pop(key, None)
-                if handle is not None:
-                    _capi.lib().glabc_rtc_release(handle)
-                if isinstance(exc, SimulatorSelfCheckError):
-                    self._failed[key] = str(exc)
-                raise
-        return self._programs[key]
+        return self._cached_program(key, ("glabc_rtc_compile_weighted_predictive", self._source_and_dimensions),
+                                    self.self_check_weighted_predictive, remember_uncompiled=True)
 
     def self_check_weighted_predictive(self, handle, seed=20240229):
         """weighted_predictive_kernel of a freshly compiled weighted predictive program against integer sums of the multiplicity m over

@@ -1,5 +1,5 @@
-"""Which kernels a run-time compiled MIXTURE program holds (csrc/glabc_rtc_mix_kernels.h), on the CPU: rtc_mix_kernels and
-rtc_mix_defines are pure functions of plain integers, so a small g++ driver evaluates them -- once as built, once under
+"""Which kernels a run-time compiled MIXTURE program holds (rtc_mix_kernels of csrc/glabc_rtc_tables.h), on the CPU: the slots and
+the #define block are pure functions of plain integers, so a small g++ driver evaluates them -- once as built, once under
 -fsanitize=address,undefined (a stand-alone program).  The expected rows are literals written from what glabc_rtc_kernel.h
 instantiates under GLABC_RTC_WITH_MIX; they are never printed from the header."""
 import os
@@ -13,7 +13,7 @@ GLMCMC, GLOBAL = 0, 1
 
 DRIVER = r"""
 #include <cstdio>
-#include "glabc_rtc_mix_kernels.h"
+#include "glabc_rtc_tables.h"
 using namespace glabc;
 static const char* SLOT[] = {"entry", "wide8", "wide16", "wide32", "wide64", "simulate_rows", "model_rows"};
 static_assert(sizeof SLOT / sizeof SLOT[0] == RTC_MIX_SLOTS, "a name per slot");
@@ -25,12 +25,12 @@ int main()
     RtcShape s;
     while (std::scanf("%d %d %d %d %d %d %d %d %d", &s.algo, &s.theta_dim, &s.y_dim, &s.noise_dim, &s.batch_size, &s.lanes, &s.wide, &s.gamma,
                       &s.hooks) == 9) {
-        const RtcMixKernels t = rtc_mix_kernels(s);
+        const RtcKernels t = rtc_mix_kernels(s);
         for (int i = 0; i < RTC_MIX_SLOTS; ++i)
             if (t.k[i].present)
                 std::printf("slot|%s|%s|%s|%s|%s\n", SLOT[i], t.k[i].fatal ? "fatal" : "empty", t.k[i].lowered ? "expr" : "symbol",
                             t.k[i].define ? t.k[i].define : "-", t.k[i].name.c_str());
-        std::printf("defines\n%send\n", rtc_mix_defines(s, t).c_str());
+        std::printf("defines\n%send\n", t.defines.c_str());
     }
     return 0;
 }
