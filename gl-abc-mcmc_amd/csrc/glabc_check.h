@@ -411,6 +411,18 @@ inline int check_abc_draws(const glabc_model* m, int64_t row0, const int64_t* id
     return check_abc_range(row0, ids, n, stride);
 }
 
+// ---- glabc_coverage_counts: check_abc_draws' order -- the pointers, the Model as glabc_abc_draws examines it, then the numbers.  The
+// widths' and the test rows' values are not looked at (they are on the device): a pair is what the arithmetic says it is
+inline int check_coverage_counts(const glabc_model* m, int64_t row0, int64_t n, const float* theta_star, const float* y_star,
+                                 const float* width, int64_t n_tests, int64_t test_stride, int32_t kernel, const unsigned long long* mass)
+{
+    if (!m || !mass || !theta_star || !y_star || !width) return GLABC_ERR_NULL;
+    if (int e = check_abc_model(m)) return e;
+    if (n < 0 || row0 < 0 || n_tests < 0 || test_stride < n_tests || (kernel != 0 && kernel != 1)) return GLABC_ERR_ARG;
+    if (n > GLABC_MAX_COVERAGE_DRAWS || n_tests > GLABC_MAX_COVERAGE_TESTS) return GLABC_ERR_ARG;
+    return GLABC_OK;
+}
+
 // ---- glabc_predictive_draws / glabc_predictive_counts: the Model a predictive draw is compiled for (check_abc_model's rules without
 // the prior, which is neither used nor examined), the history and the ids, in the order include/glabc.h lists the refusals; each
 // entry point adds what its own outputs ask

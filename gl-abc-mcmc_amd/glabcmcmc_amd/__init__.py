@@ -20,7 +20,7 @@ from .GLMCMC_NFs import GLMCMC_NF
 from .ESJD import esjd
 from .kernel_density import KernelDensity
 from .compiled import CompiledModel
-from . import _capi, checkpoint, compiled, diagnostics, distribution, engine, flows, generic, parallel, predictive, regression, rejection, smc, streaming, weighted
+from . import _capi, checkpoint, compiled, coverage, diagnostics, distribution, engine, flows, generic, parallel, predictive, regression, rejection, smc, streaming, weighted
 
 __all__ = ["GlobalMCMC", "MCMCRunner", "Uniform", "Gamma", "DiagGaussian", "GaussianMixture", "GLMALA", "GLMCMC",
-           "AGLMCMC", "GLMCMC_NF", "esjd", "KernelDensity", "distribution", "engine", "CompiledModel", "diagnostics", "rejection", "smc", "predictive", "regression", "weighted"]
+           "AGLMCMC", "GLMCMC_NF", "esjd", "KernelDensity", "distribution", "engine", "CompiledModel", "diagnostics", "rejection", "smc", "predictive", "regression", "weighted", "coverage"]

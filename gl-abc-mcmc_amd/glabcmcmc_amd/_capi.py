@@ -27,6 +27,7 @@ RTC_GAMMA = 1                  # glabc_rtc_compile_ex / glabc_rtc_compile_wide_e
 VERSION = 301                  # include/glabc.h GLABC_VERSION
 ABC_NOISE_KEY = 0x9E3779B97F4A7C15      # include/glabc.h GLABC_ABC_NOISE_KEY / GLABC_ABC_ACCEPT_KEY: glabc_abc_draws
 ABC_ACCEPT_KEY = 0xD1B54A32D192ED03
+COVERAGE_TEST_KEY = 0xC2B2AE3D27D4EB4F  # include/glabc.h GLABC_COVERAGE_TEST_KEY: coverage.py's default test pairs are draws under seed ^ this
 STREAM_LAYOUT = 2              # include/glabc.h GLABC_STREAM_LAYOUT
 
 FLAG_LOCAL = 1
@@ -335,6 +336,8 @@ ENTRY_POINTS = {
     "glabc_cross_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_abc_draws": (C.c_int, [_P(Model), C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "glabc_coverage_counts": (C.c_int, [_P(Model), C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "glabc_predictive_draws": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,
                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "glabc_predictive_counts": (C.c_int, [_P(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,

@@ -852,6 +852,49 @@ int glabc_cross_moments(const float* history, int64_t n_rows, int32_t theta_dim,
 int glabc_abc_draws(const glabc_model* model, uint64_t seed, int64_t row0, const int64_t* ids, int64_t n, int64_t stride,
                     float* theta_out, float* y_out, float* dis_out, uint8_t* accept_out, void* stream);
 
+/* ---- coverage checks on pseudo-observed data: is epsilon small enough for the credible intervals to be trusted?  One fused kernel
+ * (csrc/glabc_coverage.hip; glabcmcmc_amd/coverage.py forms ranks, rank histograms and interval coverage from its sums).  For R test
+ * pairs (theta*, y*) with y* simulated from theta*, ABC is run against each y* as if it were the observation, on one table of n prior
+ * draws that is never stored: a draw is a function of (model, seed, id), so the table is regenerated in registers and all that
+ * reaches memory is 2 + theta_dim integers per test.
+ *
+ * Table draw i < n has the id row0 + i; its (theta_i, y_i) are exactly glabc_abc_draws' theta and y of that id under `seed`: the same
+ * Philox keys (seed, seed ^ GLABC_ABC_NOISE_KEY), the same prior draw, the same simulator -- the same bits.
+ * Test r < n_tests is row r of the DEVICE arrays theta_star[j * test_stride + r] (j < theta_dim), y_star[j * test_stride + r]
+ * (j < y_dim) and width[r]: dimension-major with stride test_stride >= n_tests, the layout glabc_abc_draws writes, so its outputs pass
+ * straight in; columns n_tests .. test_stride - 1 are never read.
+ *
+ * Specification of the pair (r, i), every operator one rounded float32 operation (no FMA: -ffp-contract=off):
+ *     d = glabc_model_discrepancy of y_i for a Model whose y_obs is y*_r (the Model's own y_obs is not read)
+ *     kernel 0 (hard):   m = d <= width_r ? 1 : 0                       a NaN on either side gives 0
+ *     kernel 1 (model):  e = (d - 0.0f) / width_r;  p = glabc_expf(-(0.5f * (e * e)));  m = (uint32)rintf(p * 65536.0f), a NaN p: 0
+ *                        glabc_abc_draws' K(d) / K(0) at the test's width used as an importance weight quantised to 2^-16 -- no
+ *                        uniform is drawn, so it adds no Monte-Carlo noise and stays exact; m <= 65536
+ * m is an integer, and the outputs are integer sums over the table, ADDED to what the arrays hold (the caller zeroes them):
+ *     mass[r]                   += sum_i m
+ *     mass2[r]                  += sum_i m * m                                                    mass2 may be NULL
+ *     below[r * theta_dim + j]  += sum_i m * [theta_ij < theta*_rj]     a float32 <: a tie or a NaN is not below.  below may be NULL:
+ *                                                                       a counting-only call that skips the theta comparisons
+ * Limits: n <= GLABC_MAX_COVERAGE_DRAWS per call (the worst sum, 2^32 x 2^30, fits 64 bits; the sums of several calls are the
+ * caller's to bound), n_tests <= GLABC_MAX_COVERAGE_TESTS.  Integer adds commute: the result depends on (model, seed, row0, n, the
+ * test rows, kernel) only, never on the launch geometry, and calls over [row0, row0 + n1) and [row0 + n1, row0 + n) add up to the call
+ * over [row0, row0 + n).
+ *
+ * Models: those of glabc_abc_draws.  Refusals, in its order; a refused call launches nothing and writes nothing:
+ *   a NULL model, mass, theta_star, y_star or width                                               GLABC_ERR_NULL
+ *   the Model's dimensions, then its kinds, as glabc_abc_draws refuses them                       GLABC_ERR_DIM, GLABC_ERR_KIND
+ *   n < 0, row0 < 0, n_tests < 0, test_stride < n_tests, kernel not 0 or 1, n > GLABC_MAX_COVERAGE_DRAWS,
+ *   n_tests > GLABC_MAX_COVERAGE_TESTS                                                            GLABC_ERR_ARG
+ * n == 0 or n_tests == 0 returns GLABC_OK and writes nothing.  The widths' values are not examined (a width of 0 keeps the pairs at
+ * distance 0 under the hard kernel; +inf keeps every pair with a distance).  GLABC_VERSION and GLABC_STREAM_LAYOUT are unchanged: no
+ * struct changes and no existing draw moves. */
+#define GLABC_MAX_COVERAGE_DRAWS (1ll << 30)
+#define GLABC_MAX_COVERAGE_TESTS (1ll << 20)
+#define GLABC_COVERAGE_TEST_KEY 0xC2B2AE3D27D4EB4Full   /* glabcmcmc_amd/coverage.py: the default test pairs are draws under seed ^ this */
+int glabc_coverage_counts(const glabc_model* model, uint64_t seed, int64_t row0, int64_t n, const float* theta_star,
+                          const float* y_star, const float* width, int64_t n_tests, int64_t test_stride, int32_t kernel,
+                          unsigned long long* mass, unsigned long long* mass2, unsigned long long* below, void* stream);
+
 /* ---- posterior predictive checks: a fresh simulation y_rep ~ p(y | theta) for every draw theta of a history, and integer summaries
  * of y_rep and of its distance to y_obs, one fused kernel family (csrc/glabc_predictive.hip; glabcmcmc_amd/predictive.py forms the
  * predictive p-values and histograms from them).  The history is glabc_autocov's: [n_rows][theta_dim][stride] float32, chain-major,
